@@ -271,6 +271,43 @@ def cpu_baseline(threads=None):
                       "(oracle/topdown.py, torch CPU ops)" % (n_img, c["S"], N)}
 
 
+DUMP_SAMPLE = 1 << 18             # --dump-outputs: elements kept of a tensor larger than this (a fixed, seeded sample)
+
+
+def _dump_sample(name, flat):
+    """`flat` (1-D host array) itself, or DUMP_SAMPLE of its elements at positions drawn from a generator seeded by `name`
+    (a parameter's key: its weights and its gradient are sampled at the same positions, in every run and every build)."""
+    if flat.size <= DUMP_SAMPLE:
+        return flat
+    import zlib
+    import numpy as np
+    idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(flat.size, DUMP_SAMPLE, replace=False))
+    return flat[idx]
+
+
+def dump_outputs(out_dir, tr, loss, grads=True):
+    """--dump-outputs DIR: what the timed path computed in its LAST timed step, as DIR/<name>.npy --
+    loss.npy (float32 [1]: the loss train_device_batch returned), param.<key>.npy (the f32 weights that step's Adam update
+    left) and, unless grads=False, grad.<key>.npy (that step's gradient of each parameter), <key> = the reference's
+    state_dict names.  Tensors above DUMP_SAMPLE elements are a fixed, seeded sample of their flattened elements (_dump_sample),
+    which keeps the whole dump near 20 MB instead of the 157 MB of the full weights and gradients."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"loss": np.asarray(loss.detach().float().reshape(1).cpu().numpy(), dtype=np.float32)}
+    a = tr.arena
+    for k in sorted(a.params):
+        arrays["param." + k] = _dump_sample(k, a.params[k].detach().reshape(-1).cpu().numpy())
+        if grads:
+            arrays["grad." + k] = _dump_sample(k, a.grad_views[k].detach().reshape(-1).cpu().numpy())
+    total = sum(v.nbytes for v in arrays.values())
+    if total > 64 << 20:
+        raise SystemExit("bench.py --dump-outputs: %d bytes, more than the 64 MB allowed" % total)
+    for name, v in arrays.items():
+        assert v.dtype in (np.float32, np.float64), (name, v.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), v)
+    return {"dir": out_dir, "files": len(arrays), "bytes": int(total)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -299,6 +336,9 @@ def main():
                     help="also time the step at this many caption rows, e.g. 80 = the per-rank size of a strong-scaling run of the 640-row "
                          "batch over 8 GPUs (secondary key `strong_scaling_probe`, never `value`; off by default so that the default "
                          "command launches the 640-row kernels only and its rocprofv3 summary averages one problem size)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last one computed (loss, updated weights, gradients) as DIR/<name>.npy "
+                         "(dump_outputs); the inputs are seeded, so two builds given the same arguments can be compared output for output")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU oracle leg (0: min(host cores, 16), the fastest setting measured on the GPU box's 256-thread host: 8->293, 16->379, 32->211, 64->110, 128->24 captions/s)")
     args = ap.parse_args()
 
@@ -403,6 +443,18 @@ def main():
     if args.features == "per-image":
         batch = per_image
     elapsed, loss = timed(batch)
+    dumped = None
+    if args.dump_outputs:
+        # (before the legs below: they train the same weights further.  A sharded data-parallel rank's f32 masters are current in
+        # its own shard only until gather_masters(), a collective; its gradient arena holds partial sums, so no gradients then)
+        sharded = bool(getattr(tr, "sharded", False))
+        if sharded:
+            tr.gather_masters()
+        torch.cuda.synchronize()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, tr, loss, grads=not sharded)
+        if world > 1:
+            dist.barrier()
     elapsed_img = None
     if args.features == "per-caption" and world == 1:
         elapsed_img, _ = timed(per_image)
@@ -544,6 +596,8 @@ def main():
                 raise SystemExit("bench.py: rccl_ranks %s != --gpus %d" % (out["rccl_ranks"], world))
         if strong is not None:
             out["strong_scaling_probe"] = strong
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         if elapsed_img is not None:
             out["per_image_features"] = {"value": round(world * N * args.steps / elapsed_img, 1), "unit": "captions/s",
                                          "ms_per_step": round(elapsed_img / args.steps * 1e3, 3),
