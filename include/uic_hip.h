@@ -64,6 +64,7 @@ int uic_version(void);
  *                        profiles/r05_*_queue_probe.txt, r05_*_comm_proxy.txt).  With this flag the step uses two queues of its
  *                        own while the loop runs (the chunks' weight gradients behind the logit layer on the side stream)
  *                        instead of three; without a communication stream the three-queue order is 0.07 ms faster
+ * Any other bit of uic_topdown_dims.recurrence is refused (UIC_EARG; uic_last_error_string() names the bit).
  * uic_topdown_dims.rnn_status: NULL, or 4 caller-allocated, caller-zeroed uint32 on the device that the persistent kernels
  * update: [0] != 0 after a bounded spin timed out (the results of that call are invalid), [1] / [2] launches that ran with
  * the XCD-local / the SAFE protocol. */

@@ -144,6 +144,82 @@ def test_product_code_never_imports_the_oracle():
     assert not top
 
 
+def _namespace_scope_statements(src):
+    """The statements of a C++ source that sit at namespace scope (outside every function, class and initialiser body; bodies
+    shown as {}), comments, literals and preprocessor lines removed."""
+    src = re.sub(r'//[^\n]*|/\*.*?\*/', ' ', src, flags=re.S)
+    src = re.sub(r'"(\\.|[^"\\])*"', '""', src)
+    src = re.sub(r"'(\\.|[^'\\])*'", "''", src)
+    src = re.sub(r'^\s*#[^\n]*(\\\n[^\n]*)*', ' ', src, flags=re.M)
+    out, cur, i = [], "", 0
+    while i < len(src):
+        ch = src[i]
+        if ch == "{":
+            if re.search(r'(\bnamespace\b[\w\s:]*|\bextern\s*"")\s*$', cur):
+                cur = ""                                 # a namespace (or extern "C") block: its statements are top-level too
+            else:
+                depth, i = 1, i + 1
+                while depth:
+                    depth += {"{": 1, "}": -1}.get(src[i], 0)
+                    i += 1
+                cur += "{}"
+                if not src[i:].lstrip().startswith((";", ",")) and "(" in cur and "=" not in cur.split("(")[0]:
+                    out.append(cur)                      # a function definition
+                    cur = ""
+                continue
+        elif ch == "}":
+            cur = ""
+        elif ch == ";":
+            out.append(cur)
+            cur = ""
+        else:
+            cur += ch
+        i += 1
+    return [" ".join(t.split()) for t in out if t.strip()]
+
+
+def _mutable_globals(src):
+    """Names of the variables a C++ source defines at namespace scope without const / constexpr."""
+    names = []
+    for st in _namespace_scope_statements(src):
+        if re.match(r"(typedef|using|template|static_assert|extern)\b", st) or re.match(r"(struct|class|union|enum)\b[^=]*\{\}$", st):
+            continue
+        head = st.split("=")[0]
+        if "(" in head:                                  # a function (declaration or definition)
+            continue
+        if re.search(r"\bconstexpr\b", head) or re.match(r"(static\s+)?const\b[^*&]*$", head) or re.search(r"\*\s*const\s+\w+\s*(\[|$)", head):
+            continue
+        m = re.search(r"(\w+)\s*(\[[^]]*\]\s*)*(\{\})?$", head.strip())
+        names.append(m.group(1) if m else head)
+    return names
+
+
+def test_weight_gradient_dispatch_keeps_no_thread_state():
+    """Where a weight gradient runs (beside the fused step's BPTT loop or alone on the chip) is an argument of every call: the
+    sources that dispatch weight gradients declare no thread_local and no mutable namespace-scope variable but the fused step's
+    per-device side streams and the mutex that guards their creation."""
+    assert _mutable_globals("namespace { int a = 0; thread_local int b; const int c = 1; constexpr int d = 2; std::mutex m; "
+                            "struct S { int x; }; S s[4]; int f(int x) { return x; } int g(int); }") == ["a", "b", "m", "s"]
+    csrc = os.path.join(ROOT, "unpaired_image_captioning_amd", "csrc")
+    allowed = {"topdown.hip": ["g_side", "g_side_mutex"]}
+    for f in ("uic_host.h", "gemm_tn.hip", "gemm_tn_pp.hip", "topdown.hip"):
+        src = open(os.path.join(csrc, f)).read()
+        assert not re.search(r"\bthread_local\b", re.sub(r"//[^\n]*", "", src)), f
+        assert _mutable_globals(src) == allowed.get(f, []), f
+
+
+def test_unknown_recurrence_bits_are_refused_by_name():
+    from unpaired_image_captioning_amd import _lib
+    lib = _lib.load()
+    d = _lib.Dims(N=640, R=36, D=2048, Dfc=2048, H=512, E=512, A=512, V1=9488, T=17, dtype=1, drop_p=0.5,
+                  recurrence=_lib.REC_COMM_STREAM | _lib.REC_EARLY_GRADS)
+    assert lib.uic_topdown_workspace_bytes(C.byref(d)) > 0
+    for bit in (0x80, 0x200, 0x4000, 1 << 30):
+        d.recurrence = _lib.REC_COMM_STREAM | bit
+        assert lib.uic_topdown_workspace_bytes(C.byref(d)) == 0, hex(bit)
+        assert ("0x%x" % bit).encode() in lib.uic_last_error_string(), hex(bit)
+
+
 def test_unsupported_options_raise():
     from unpaired_image_captioning_amd import models
     with pytest.raises(ValueError):

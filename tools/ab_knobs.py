@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """A/B of launch orders of the fused training step in ONE process on ONE device (cdna guide rule 24): the settings --
-uic_topdown_dims.recurrence values, incl. the measurement knobs of csrc/uic_common.h (UIC_KNOB_*) -- alternate in blocks of
-steps; per setting the wall time per step (median and min over the rounds) and the step's own timing marks.
-    python tools/ab_knobs.py 0 0x100 0x200 [--steps 20] [--rounds 6]"""
+uic_topdown_dims.recurrence values (the UIC_REC_* flags of include/uic_hip.h) -- alternate in blocks of steps; per setting the
+wall time per step (median and min over the rounds) and the step's own timing marks.
+    python tools/ab_knobs.py 0 64 16 [--steps 20] [--rounds 6]     (default order, UIC_REC_COMM_STREAM, UIC_REC_EARLY_GRADS)"""
 import argparse
 import os
 import sys

@@ -29,7 +29,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--workgroups", type=int, default=16)
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--world", type=int, default=8, help="the world size the stand-in pretends (Adam runs on 1/world of the arena)")
-ap.add_argument("--rec", default="0", help="extra uic_topdown_dims.recurrence bits (measurement knobs, csrc/uic_common.h)")
+ap.add_argument("--rec", default="0", help="extra uic_topdown_dims.recurrence bits (UIC_REC_* of include/uic_hip.h)")
 ap.add_argument("--no-next-den", action="store_true", help="do not carry the next batch's mask sum in the step's all-reduce (a 1-float "
                 "collective then sits in front of every forward pass)")
 ap.add_argument("--only", default="", help="sharded | allreduce | none: only that exchange / only the step without one (for traces)")

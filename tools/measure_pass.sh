@@ -76,7 +76,7 @@ echo "--- --compressed" >> $O/loader_bench.txt
 timeout 300 python3 $R/tools/loader_bench.py --compressed >> $O/loader_bench.txt 2>&1
 tail -12 $O/loader_bench.txt
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 $R/tools/micro/mfma_agpr.hip -o /tmp/mfma_agpr 2>/dev/null && timeout 100 /tmp/mfma_agpr > $O/mfma_agpr.txt 2>&1
-timeout 200 python3 $R/tools/ab_knobs.py 0 0x200 0x600 > $O/ab_knobs.txt 2>&1
+timeout 200 python3 $R/tools/ab_knobs.py 0 64 > $O/ab_knobs.txt 2>&1
 cat $O/ab_knobs.txt
 # round 5 (second half): per-phase stamps of the pivot decoder's persistent launches; what a dependent launch costs
 timeout 300 python3 $R/tools/nmt_bwd_probe.py > $O/nmt_bwd_probe.txt 2>&1

@@ -760,13 +760,8 @@ int launch_glds(const UicGemmParams& p, hipStream_t s) {
   // it took two 64-KB ones, and beside the side streams' 128-KB workgroups the launch then waits for 240 free CUs instead of 120 --
   // so the ring stops at 192 workgroups.  Alone on the chip it makes a K round cost 0.3 us instead of 0.8 (tools/gemm_headroom.py).
   const int rounds = p.seg[0].K / (128 / (int)sizeof(T)) / (p.splitk > 1 ? p.splitk : 1);
-#ifdef UIC_GLDS_NO_RING           // (A/B builds: tools/build_variant.sh)
-  const bool ring = false;
-  (void)rounds;
-#else
   const long wgs = (long)grid.x * grid.y * grid.z;
   const bool ring = ((wgs <= 192 && rounds >= 3) || (wgs <= 256 && rounds >= 32)) && !(p.flags & UIC_GEMM_NO_RING);   // (long K loops: also at one workgroup per CU)
-#endif
   if (ring) hipLaunchKernelGGL((uic_gemm_glds_kernel<T, 3>), grid, dim3(256), 98304, s, p);
   else hipLaunchKernelGGL((uic_gemm_glds_kernel<T, 2>), grid, dim3(256), 65536, s, p);
   UIC_LAUNCH_CHECK("uic_gemm_glds_kernel");

@@ -20,9 +20,6 @@
 #include <type_traits>
 #include <stdlib.h>
 
-thread_local int g_uic_tn_ring_off = 0;
-thread_local int g_uic_knobs = 0;
-
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
@@ -363,7 +360,7 @@ bool uic_gemm_tn_eligible(const UicGemmTnParams& p) {
   return n == p.N;
 }
 
-int uic_gemm_tn_launch(const UicGemmTnParams& p, hipStream_t s) {
+int uic_gemm_tn_launch(const UicGemmTnParams& p, hipStream_t s, UicWgPlace at) {
   UIC_REQUIRE(uic_gemm_tn_eligible(p), "gemm_tn: shape M=%d N=%d K=%d not eligible (K %% 64, segment widths %% 128, 16-byte alignment)", p.M, p.N, p.K);
   UIC_REQUIRE(p.splitk >= 1 && (p.slab || (p.splitk == 1 && p.ndst > 0)), "gemm_tn: needs a slab (or direct destinations with splitk == 1)");
   static bool configured = false;
@@ -375,7 +372,7 @@ int uic_gemm_tn_launch(const UicGemmTnParams& p, hipStream_t s) {
     configured = true;
   }
   dim3 grid((p.M + 127) / 128, (p.N + 127) / 128, p.splitk);
-  const int ring_max = g_uic_tn_ring_off ? 0 : 256;     // workgroups: at most one per CU
+  const int ring_max = at == UIC_WG_ALONE ? 256 : 0;   // workgroups: at most one per CU
   const long wgs = (long)grid.x * grid.y * grid.z;
   if (wgs <= ring_max && p.K / 64 / (p.splitk > 1 ? p.splitk : 1) >= 8)
     hipLaunchKernelGGL(uic_gemm_tn_kernel<4>, grid, dim3(256), 131072, s, p);

@@ -23,20 +23,8 @@
 
 namespace {
 
-#ifndef UIC_WG_CHUNK
-#define UIC_WG_CHUNK 4
-#endif
-constexpr int WG_CHUNK = UIC_WG_CHUNK;   // decode steps per hand-off between the two streams of the fused training step
-#ifndef UIC_BPTT_SPLIT
-#define UIC_BPTT_SPLIT 4
-#endif
-#ifndef UIC_BPTT_FUSE_CELL
-#define UIC_BPTT_FUSE_CELL 1
-#endif
-#ifndef UIC_GFC_SEPARATE
-#define UIC_GFC_SEPARATE 1
-#endif
-constexpr int BPTT_SPLIT = UIC_BPTT_SPLIT;   // K slices of the BPTT loop's d x GEMMs (Step::bptt_split)
+constexpr int WG_CHUNK = 4;     // decode steps per hand-off between the two streams of the fused training step
+constexpr int BPTT_SPLIT = 4;   // K slices of the BPTT loop's d x GEMMs (Step::bptt_split)
 
 struct Layout {
   // forward activations
@@ -70,7 +58,7 @@ struct Layout {
   void* tLA; void* tLB; float* colscratchL;   // scratch of the logit-layer weight gradients (side stream)
   void* tSA; void* tSB; float* slab2;         // scratch of the per-chunk recurrent weight gradients (side stream)
   void* tTA; void* tTB; float* slab3;         // the same for the third stream (att_lstm / h2att share of a chunk)
-  void* tUA; void* tUB; float* slab4;         // ... and the fourth (default order: the chunks' shares run on streams 3 and 4)
+  void* tUA; void* tUB; float* slab4;         // ... and the third stream's second set (default order: a chunk's att_lstm / h2att share)
   int* embed_scratch;                         // uic_embed_bwd_sorted_launch
   void* fcwT; void* attwT;                     // fc_embed / att_embed weights transposed ([Dfc, H], [D, H]): only for the optional input-feature gradients
   void* ones_blk; size_t ones_rows;           // [max(WG_CHUNK * N, N * R), 128] operand dtype, all ones: the "input" whose weight gradient is the bias gradient
@@ -322,6 +310,10 @@ int check_dims(const uic_topdown_dims* d) {
               UIC_MAX_LOGIT_LAYERS);
   UIC_REQUIRE(d->seq_per_img >= 0 && (d->seq_per_img <= 1 || d->N % d->seq_per_img == 0),
               "seq_per_img=%d must divide N=%d", d->seq_per_img, d->N);
+  const int rec_known = UIC_REC_FWD_CHAIN | UIC_REC_BWD_PERSIST | UIC_REC_SAFE | UIC_REC_STAMPS | UIC_REC_EARLY_GRADS | UIC_REC_NO_F32A |
+                        UIC_REC_COMM_STREAM;
+  UIC_REQUIRE((d->recurrence & ~rec_known) == 0, "recurrence=0x%x: unknown bit(s) 0x%x (the UIC_REC_* flags of uic_hip.h)",
+              (unsigned)d->recurrence, (unsigned)(d->recurrence & ~rec_known));
   return UIC_OK;
 }
 
@@ -468,8 +460,6 @@ struct SideStream {
   hipStream_t stream = nullptr;
   hipStream_t stream3 = nullptr;    // a chunk's att_lstm / h2att weight gradients beside its lang_lstm ones (independent GEMMs)
   hipEvent_t ev_s3 = nullptr;       // stream3 -> side: that share of every chunk so far is done
-  hipStream_t stream4 = nullptr;    // default order: lang_lstm share of a chunk on stream3, att_lstm / h2att share on stream4
-  hipEvent_t ev_s4 = nullptr;       // stream4 -> stream3: its share of every chunk is done
   hipEvent_t ev_prep = nullptr;     // side -> stream3: the embedding gradient's token bucketing is done
   hipEvent_t ev_den = nullptr, ev_done = nullptr;
   hipEvent_t ev_pro3 = nullptr;     // third stream: its branch of the forward prologue (fc_embed, Gfc, initial state) is through
@@ -527,9 +517,7 @@ int get_side(SideStream** out) {
     // stream, these two and ONE more stream of the caller -- its communication stream -- a busy extra stream costs nothing; with a
     // fifth stream in existence, used or not, the same extra stream makes the step 0.7 ms longer).  The last chunk's second share
     // therefore runs behind the first on stream 3.
-    ss.stream4 = ss.stream3;
     UIC_TRY(uic_check_hip(hipEventCreateWithFlags(&ss.ev_s3, hipEventDisableTiming), "hipEventCreate"));
-    UIC_TRY(uic_check_hip(hipEventCreateWithFlags(&ss.ev_s4, hipEventDisableTiming), "hipEventCreate"));
     UIC_TRY(uic_check_hip(hipEventCreateWithFlags(&ss.ev_prep, hipEventDisableTiming), "hipEventCreate"));
     UIC_TRY(uic_check_hip(hipEventCreateWithFlags(&ss.ev_den, hipEventDisableTiming), "hipEventCreate"));
     UIC_TRY(uic_check_hip(hipEventCreateWithFlags(&ss.ev_done, hipEventDisableTiming), "hipEventCreate"));
@@ -889,7 +877,7 @@ struct Step {
   // gfc_separate: the persistent recurrence adds the caption row's fc' term (Gfc) itself, so the batched input GEMM (the long
   // pole of the prologue's side-stream branch) no longer queues behind cast -> fc_embed -> Gfc; the launch chain keeps Gfc
   // folded into Gx (one operand less per step).  Same f32 additions in the same order either way.
-  bool gfc_separate() const { return UIC_GFC_SEPARATE && persist_ok(); }
+  bool gfc_separate() const { return persist_ok(); }
   int fwd_embed(hipStream_t s) {
     // xt_t = dropout(relu(embed[labels[:, t]])) for all steps (AttModel.py:145,160)
     return uic_embed_fwd_t_launch(dt, dv.embed_w, dt, V1, E, b->labels, b->ld_labels, N, t_run, drop_p, seed, UIC_SITE_EMBED, 0, 1, L.xt_all, s);
@@ -1179,8 +1167,9 @@ struct Step {
     }
     return UIC_OK;
   }
-  // d W_logit, d b_logit over all executed steps (own scratch buffers: may run beside the BPTT loop)
-  int logit_weight_grads(hipStream_t s, bool side = false) {
+  // d W_logit, d b_logit over all executed steps (own scratch buffers; beside the BPTT loop: the side stream's slab)
+  int logit_weight_grads(hipStream_t s, UicWgPlace at) {
+    float* const slab = at == UIC_WG_ALONE ? L.slab : L.slab2;
     if (compact) {
       const int K = live_pad();
       if (K == 0) {
@@ -1190,19 +1179,19 @@ struct Step {
       }
       const UicGemmTnSeg seg{L.hc, H, H};
       const WDest d1{G->logit_w, H, 0, H};
-      UIC_TRY(wgrad_group(side ? L.slab2 : L.slab, L.dlogits, V1p, V1, &seg, 1, K, &d1, 1, s, false, L.tLA, L.tLB));
+      UIC_TRY(wgrad_group(slab, L.dlogits, V1p, V1, &seg, 1, K, &d1, 1, s, false, L.tLA, L.tLB, at));
       return uic_colsum_launch(dt, L.dlogits, K, V1, V1p, G->logit_b, L.colscratchL, L.colscratch_floats, s);
     }
     {
       const UicGemmTnSeg seg{logit_in_all(), H, H};
       const WDest d1{G->logit_w, H, 0, H};
-      UIC_TRY(wgrad_group(side ? L.slab2 : L.slab, L.dlogits, V1p, V1, &seg, 1, Meff, &d1, 1, s, false, L.tLA, L.tLB));
+      UIC_TRY(wgrad_group(slab, L.dlogits, V1p, V1, &seg, 1, Meff, &d1, 1, s, false, L.tLA, L.tLB, at));
     }
     for (int l = 0; l < nlh(); ++l) {
       UIC_REQUIRE(G->logit_h_w[l] && G->logit_h_b[l], "backward: logit_layers=%d needs gradient tensors for hidden block %d", d.logit_layers, l);
       const UicGemmTnSeg seg{l ? L.lh[l - 1] : L.hdrop_all, H, H};
       const WDest d1{G->logit_h_w[l], H, 0, H};
-      UIC_TRY(wgrad_group(side ? L.slab2 : L.slab, L.dlh_pre[l], H, H, &seg, 1, Meff, &d1, 1, s, false, L.tLA, L.tLB));
+      UIC_TRY(wgrad_group(slab, L.dlh_pre[l], H, H, &seg, 1, Meff, &d1, 1, s, false, L.tLA, L.tLB, at));
       UIC_TRY(uic_colsum_launch(dt, L.dlh_pre[l], Meff, H, H, G->logit_h_b[l], L.colscratchL, L.colscratch_floats, s));
     }
     return uic_colsum_launch(dt, L.dlogits, Meff, V1, V1p, G->logit_b, L.colscratchL, L.colscratch_floats, s);
@@ -1262,7 +1251,7 @@ struct Step {
   // 15.2 -> 12.7 us and 14.5 -> 11.6 us per launch isolated (profiles/r03_v2_gemm_headroom.txt).  0: small problems, direct GEMMs.
   int bptt_split() const {
     const int rounds = H4 / (dt == UIC_BF16 ? 64 : 32);
-    return (BPTT_SPLIT > 1 && N >= 256 && H % 128 == 0 && uic_gemm_glds_eligible(dt, H4) && rounds % BPTT_SPLIT == 0 && rounds / BPTT_SPLIT >= 4) ? BPTT_SPLIT : 0;
+    return (N >= 256 && H % 128 == 0 && uic_gemm_glds_eligible(dt, H4) && rounds % BPTT_SPLIT == 0 && rounds / BPTT_SPLIT >= 4) ? BPTT_SPLIT : 0;
   }
 
   int bwd_step(int t, hipStream_t s) {
@@ -1305,9 +1294,7 @@ struct Step {
       if (S) { a.dctx_nslab = S; a.dctx_slab_stride = st2; a.dctx_sum = dx2; a.ld_dctx_sum = 3 * H; }
       a.de = L.de_all + (size_t)t * N * R;
       a.d_att_h = offw(L.datth_all, (size_t)t * N * A, dt);
-#ifndef UIC_NO_DEAD_ROWS              // (A/B builds)
       if (have_len) { a.row_len = L.cap_len; a.step = t; }
-#endif
       UIC_TRY(uic_attention_bwd_step_launch(a, s));
     }
     UicH2attCellParams hc;
@@ -1321,7 +1308,7 @@ struct Step {
       hc.c_prev = L.c_att + t * NH; hc.c = L.c_att + (t + 1) * NH;
       hc.dgates = offw(L.dg1_all, (size_t)t * N * H4, dt);
     }
-    const bool fused_cell = UIC_BPTT_FUSE_CELL && S && uic_h2att_cell_bwd_eligible(hc);
+    const bool fused_cell = S && uic_h2att_cell_bwd_eligible(hc);
     if (fused_cell) {
       UIC_TRY(uic_h2att_cell_bwd_launch(hc, s));
     } else {
@@ -1360,27 +1347,30 @@ struct Step {
   // data-parallel caller can start exchanging the early group (LSTMs, embedding, fc_embed; with the logit layer
   // > 85 % of the bytes) while the late group (h2att, alpha_net, ctx2att, att_embed) is still being computed
   int bwd_epilogue(hipStream_t s) {
-    UIC_TRY(bwd_epilogue_early(s));
-    return bwd_epilogue_late(s);
+    UIC_TRY(bwd_epilogue_early(s, UIC_WG_ALONE));
+    return bwd_epilogue_late(s, UIC_WG_ALONE);
   }
+  // (at: where the weight gradients run, beside the BPTT chain or alone on the chip -- every method that issues them takes it
+  // from its caller)
   int wgrad_group(float* slab, const void* A, int lda, int lrows, const UicGemmTnSeg* segs, int nseg, int rows, const WDest* dst,
-                  int nd, hipStream_t s, bool accumulate, void* tA, void* tB) {
-    return ::wgrad_group(slab, L.slab_bytes, dt, A, lda, lrows, segs, nseg, rows, dst, nd, s, accumulate, tA, tB);
+                  int nd, hipStream_t s, bool accumulate, void* tA, void* tB, UicWgPlace at) {
+    return ::wgrad_group(slab, L.slab_bytes, dt, A, lda, lrows, segs, nseg, rows, dst, nd, s, accumulate, tA, tB, at);
   }
 
   // recurrent weight gradients (both LSTMs' weights and h2att) restricted to decode steps [t0, t1): one chunk of the
   // stacked-row GEMMs, accumulated into G unless `first`.  Used by the fused step on the side stream, chunk by chunk
   // behind the BPTT loop, so that only the last chunk's share is left when the loop ends.
-  // sb (optional): a second stream for the att_lstm / h2att share, with scratch of its own (the GEMMs are independent)
-  // own34: both shares away from the side stream -- lang_lstm on `s` with the third stream's scratch, att_lstm / h2att on `sb`
-  // with the fourth's (the default order of the fused step: the side stream keeps the logit layer)
-  int wgrad_chunk(int t0, int t1, bool first, hipStream_t s, hipStream_t sb = nullptr, bool own34 = false) {
-    float* const slabA = own34 ? L.slab3 : L.slab2;
-    void* const tAA = own34 ? L.tTA : L.tSA;
-    void* const tAB = own34 ? L.tTB : L.tSB;
-    float* const slabB = own34 ? L.slab4 : sb ? L.slab3 : L.slab2;
-    void* const tBA = own34 ? L.tUA : sb ? L.tTA : L.tSA;
-    void* const tBB = own34 ? L.tUB : sb ? L.tTB : L.tSB;
+  // third: `s` is the third stream (the default order of the fused step: the side stream keeps the logit layer), which runs both
+  // shares with its two scratch sets; else `s` is the side stream
+  // sb (optional, the early-gradient order): the third stream for the att_lstm / h2att share, with its scratch (the GEMMs are
+  // independent)
+  int wgrad_chunk(int t0, int t1, bool first, UicWgPlace at, hipStream_t s, bool third, hipStream_t sb = nullptr) {
+    float* const slabA = third ? L.slab3 : L.slab2;
+    void* const tAA = third ? L.tTA : L.tSA;
+    void* const tAB = third ? L.tTB : L.tSB;
+    float* const slabB = third ? L.slab4 : sb ? L.slab3 : L.slab2;
+    void* const tBA = third ? L.tUA : sb ? L.tTA : L.tSA;
+    void* const tBB = third ? L.tUB : sb ? L.tTB : L.tSB;
     if (!sb) sb = s;
     const int rows = (t1 - t0) * N;
     const size_t r0 = (size_t)t0 * N;
@@ -1393,30 +1383,30 @@ struct Step {
       // weight gradient IS the column sum -- one more column tile per row tile instead of two column-sum passes in the tail
       const UicGemmTnSeg segs[4] = {{ctx, H, H}, {h_att_new, H, H}, {h_lang_prev, H, H}, {L.ones_blk, 128, 128}};
       const WDest dd[3] = {{G->lang_lstm_w_ih, 2 * H, 0, 2 * H}, {G->lang_lstm_w_hh, H, 2 * H, H}, {G->lang_lstm_b_ih, 1, 3 * H, 1}};
-      UIC_TRY(wgrad_group(slabA, off(L.dg2_all, r0 * H4, dt), H4, H4, segs, 4, rows, dd, 3, s, !first, tAA, tAB));
+      UIC_TRY(wgrad_group(slabA, off(L.dg2_all, r0 * H4, dt), H4, H4, segs, 4, rows, dd, 3, s, !first, tAA, tAB, at));
     } else {  // lang_lstm: dG2^T x [att_res | h_att | h_lang_prev]
       const UicGemmTnSeg segs[3] = {{ctx, H, H}, {h_att_new, H, H}, {h_lang_prev, H, H}};
       const WDest dd[2] = {{G->lang_lstm_w_ih, 2 * H, 0, 2 * H}, {G->lang_lstm_w_hh, H, 2 * H, H}};
-      UIC_TRY(wgrad_group(slabA, off(L.dg2_all, r0 * H4, dt), H4, H4, segs, 3, rows, dd, 2, s, !first, tAA, tAB));
+      UIC_TRY(wgrad_group(slabA, off(L.dg2_all, r0 * H4, dt), H4, H4, segs, 3, rows, dd, 2, s, !first, tAA, tAB, at));
     }
     if (bias_in_chunks() && A % 128 == 0) {  // h2att: d_att_h^T x [h_att | ones]
       const UicGemmTnSeg segs[2] = {{h_att_new, H, H}, {L.ones_blk, 128, 128}};
       const WDest dd[2] = {{G->h2att_w, H, 0, H}, {G->h2att_b, 1, H, 1}};
-      UIC_TRY(wgrad_group(slabB, off(L.datth_all, r0 * A, dt), A, A, segs, 2, rows, dd, 2, sb, !first, tBA, tBB));
+      UIC_TRY(wgrad_group(slabB, off(L.datth_all, r0 * A, dt), A, A, segs, 2, rows, dd, 2, sb, !first, tBA, tBB, at));
     } else {  // h2att: d_att_h^T x h_att
       const UicGemmTnSeg seg{h_att_new, H, H};
       const WDest d1{G->h2att_w, H, 0, H};
-      UIC_TRY(wgrad_group(slabB, off(L.datth_all, r0 * A, dt), A, A, &seg, 1, rows, &d1, 1, sb, !first, tBA, tBB));
+      UIC_TRY(wgrad_group(slabB, off(L.datth_all, r0 * A, dt), A, A, &seg, 1, rows, &d1, 1, sb, !first, tBA, tBB, at));
     }
     if (bias_in_chunks()) {
       const UicGemmTnSeg segs[4] = {{h_lang_prev, H, H}, {off(L.xt_all, r0 * E, dt), E, E}, {h_att_prev, H, H}, {L.ones_blk, 128, 128}};
       const WDest dd[4] = {{G->att_lstm_w_ih, ldih, 0, H}, {G->att_lstm_w_ih + 2 * H, ldih, H, E}, {G->att_lstm_w_hh, H, H + E, H},
                            {G->att_lstm_b_ih, 1, 2 * H + E, 1}};
-      UIC_TRY(wgrad_group(slabB, off(L.dg1_all, r0 * H4, dt), H4, H4, segs, 4, rows, dd, 4, sb, !first, tBA, tBB));
+      UIC_TRY(wgrad_group(slabB, off(L.dg1_all, r0 * H4, dt), H4, H4, segs, 4, rows, dd, 4, sb, !first, tBA, tBB, at));
     } else {  // att_lstm: dG1^T x [h_lang_prev | xt | h_att_prev]
       const UicGemmTnSeg segs[3] = {{h_lang_prev, H, H}, {off(L.xt_all, r0 * E, dt), E, E}, {h_att_prev, H, H}};
       const WDest dd[3] = {{G->att_lstm_w_ih, ldih, 0, H}, {G->att_lstm_w_ih + 2 * H, ldih, H, E}, {G->att_lstm_w_hh, H, H + E, H}};
-      UIC_TRY(wgrad_group(slabB, off(L.dg1_all, r0 * H4, dt), H4, H4, segs, 3, rows, dd, 3, sb, !first, tBA, tBB));
+      UIC_TRY(wgrad_group(slabB, off(L.dg1_all, r0 * H4, dt), H4, H4, segs, 3, rows, dd, 3, sb, !first, tBA, tBB, at));
     }
     return UIC_OK;
   }
@@ -1433,11 +1423,11 @@ struct Step {
   //   fc_cols_grad: dGfc = sum_t dG1_t (left in L.dgfc) -> the fc' columns of att_lstm.weight_ih, which completes that matrix;
   //   embed_grad(half): d xt = dG1 Wx of the decode steps of one half of the bucketed position list (embed_split; 0: all
   //                     steps at once) -> their share of the embedding table.
-  int fc_cols_grad(hipStream_t s, float* slab, void* tA, void* tB) {
+  int fc_cols_grad(hipStream_t s, float* slab, void* tA, void* tB, UicWgPlace at) {
     UIC_TRY(uic_sum_steps_launch(dt, L.dg1_all, t_run, (size_t)N * H4, L.dgfc, s));
     const UicGemmTnSeg seg{L.fcp, H, H};
     const WDest d1{G->att_lstm_w_ih + H, ldih, 0, H};
-    return wgrad_group(slab, L.dgfc, H4, H4, &seg, 1, N, &d1, 1, s, false, tA, tB);
+    return wgrad_group(slab, L.dgfc, H4, H4, &seg, 1, N, &d1, 1, s, false, tA, tB, at);
   }
   int embed_grad(int half, hipStream_t s) {
     const int t0 = embed_split && half ? embed_split : 0, t1 = embed_split && !half ? embed_split : t_run;
@@ -1461,7 +1451,7 @@ struct Step {
     UIC_TRY(uic_copy_launch(G->lang_lstm_b_hh, G->lang_lstm_b_ih, (size_t)H4 * 4, s));
     return uic_copy_launch(G->att_lstm_b_hh, G->att_lstm_b_ih, (size_t)H4 * 4, s);
   }
-  int bwd_epilogue_early(hipStream_t s, bool chunked = false, bool side = false, bool first_done = false, bool bias_copies = true) {
+  int bwd_epilogue_early(hipStream_t s, UicWgPlace at, bool chunked = false, bool side = false, bool first_done = false, bool bias_copies = true) {
     void* const tA = side ? L.tSA : L.tA;
     void* const tB = side ? L.tSB : L.tB;
     float* const colscratch = side ? L.colscratchL : L.colscratch;
@@ -1472,7 +1462,7 @@ struct Step {
     if (!chunked) {
       const UicGemmTnSeg segs[3] = {{L.ctx_all, H, H}, {off(L.h_att, NH, dt), H, H}, {L.h_lang, H, H}};
       const WDest dd[2] = {{G->lang_lstm_w_ih, 2 * H, 0, 2 * H}, {G->lang_lstm_w_hh, H, 2 * H, H}};
-      UIC_TRY(wgrad_group(slab, L.dg2_all, H4, H4, segs, 3, Meff, dd, 2, s, false, tA, tB));
+      UIC_TRY(wgrad_group(slab, L.dg2_all, H4, H4, segs, 3, Meff, dd, 2, s, false, tA, tB, at));
     }
     if (!(chunked && bias_in_chunks()))
       UIC_TRY(uic_colsum_launch(dt, L.dg2_all, Meff, H4, H4, G->lang_lstm_b_ih, colscratch, L.colscratch_floats, s));
@@ -1481,13 +1471,13 @@ struct Step {
     if (!chunked) {
       const UicGemmTnSeg segs[3] = {{L.h_lang, H, H}, {L.xt_all, E, E}, {L.h_att, H, H}};
       const WDest dd[3] = {{G->att_lstm_w_ih, ldih, 0, H}, {G->att_lstm_w_ih + 2 * H, ldih, H, E}, {G->att_lstm_w_hh, H, H + E, H}};
-      UIC_TRY(wgrad_group(slab, L.dg1_all, H4, H4, segs, 3, Meff, dd, 3, s, false, tA, tB));
+      UIC_TRY(wgrad_group(slab, L.dg1_all, H4, H4, segs, 3, Meff, dd, 3, s, false, tA, tB, at));
     }
     if (!(chunked && bias_in_chunks()))
       UIC_TRY(uic_colsum_launch(dt, L.dg1_all, Meff, H4, H4, G->att_lstm_b_ih, colscratch, L.colscratch_floats, s));
     if (bias_copies) UIC_TRY(uic_copy_launch(G->att_lstm_b_hh, G->att_lstm_b_ih, (size_t)H4 * 4, s));
     if (!first_done) {
-      UIC_TRY(fc_cols_grad(s, slab, tA, tB));
+      UIC_TRY(fc_cols_grad(s, slab, tA, tB, at));
       UIC_TRY(embed_grad(0, s));
     }
     {  // d fc' from dGfc (left in L.dgfc by fc_cols_grad)
@@ -1500,7 +1490,7 @@ struct Step {
     {
       const UicGemmTnSeg seg{fc_in, Dfc, Dfc};
       const WDest d1{G->fc_w, Dfc, 0, Dfc};
-      UIC_TRY(wgrad_group(slab, L.dfcpre, H, H, &seg, 1, N, &d1, 1, s, false, tA, tB));
+      UIC_TRY(wgrad_group(slab, L.dfcpre, H, H, &seg, 1, N, &d1, 1, s, false, tA, tB, at));
     }
     UIC_TRY(uic_colsum_launch(dt, L.dfcpre, N, H, H, G->fc_b, colscratch, L.colscratch_floats, s));
     if (b->d_fc_feats) {   // optional: d fc_feats = d fc_pre W_fc, the S caption rows of an image summed (row i S + k of d fc_pre: lda = S H)
@@ -1517,12 +1507,12 @@ struct Step {
   }
   // part: 0 = everything, 1 = only the deferred attention accumulation, 2 = everything else.  (Measured: running the
   // accumulation -- whole-CU workgroups -- before releasing the side stream's tail is 3 % SLOWER than letting both run.)
-  int bwd_epilogue_late(hipStream_t s, bool chunked = false, int part = 0) {
+  int bwd_epilogue_late(hipStream_t s, UicWgPlace at, bool chunked = false, int part = 0) {
     // h2att
     if (!chunked && part != 1) {
       const UicGemmTnSeg seg{off(L.h_att, NH, dt), H, H};
       const WDest d1{G->h2att_w, H, 0, H};
-      UIC_TRY(wgrad_group(L.slab, L.datth_all, A, A, &seg, 1, Meff, &d1, 1, s, false, L.tA, L.tB));
+      UIC_TRY(wgrad_group(L.slab, L.datth_all, A, A, &seg, 1, Meff, &d1, 1, s, false, L.tA, L.tB, at));
       UIC_TRY(uic_colsum_launch(dt, L.datth_all, Meff, A, A, G->h2att_b, L.colscratch, L.colscratch_floats, s));
     }
     if (part != 2) {  // attention: deferred accumulation over steps
@@ -1533,9 +1523,7 @@ struct Step {
       a.dctx_all = L.dx2_all; a.lddctx = 3 * H; a.dctx_step_stride = (size_t)N * 3 * H;
       a.p_att = L.patt; a.w_alpha = w->alpha_w;
       a.d_att = L.d_att; a.d_p_att = L.d_patt; a.d_walpha_part = L.dwalpha_part;
-#ifndef UIC_NO_DEAD_ACCUM             // (A/B builds)
       if (have_len) a.row_len = L.cap_len;     // (steps behind a caption's end add zeros)
-#endif
       UIC_TRY(uic_attention_bwd_accum_launch(a, s));
       UIC_TRY(uic_colsum_small_launch(L.dwalpha_part, N, A + 1, A, G->alpha_w, G->alpha_b, s));
     }
@@ -1545,11 +1533,11 @@ struct Step {
     if (ones_ok) {
       const UicGemmTnSeg segs[2] = {{L.attp, H, H}, {L.ones_blk, 128, 128}};
       const WDest dd[2] = {{G->ctx2att_w, H, 0, H}, {G->ctx2att_b, 1, H, 1}};
-      UIC_TRY(wgrad_group(L.slab, L.d_patt, A, A, segs, 2, NR, dd, 2, s, false, L.tA, L.tB));
+      UIC_TRY(wgrad_group(L.slab, L.d_patt, A, A, segs, 2, NR, dd, 2, s, false, L.tA, L.tB, at));
     } else {
       const UicGemmTnSeg seg{L.attp, H, H};
       const WDest d1{G->ctx2att_w, H, 0, H};
-      UIC_TRY(wgrad_group(L.slab, L.d_patt, A, A, &seg, 1, NR, &d1, 1, s, false, L.tA, L.tB));
+      UIC_TRY(wgrad_group(L.slab, L.d_patt, A, A, &seg, 1, NR, &d1, 1, s, false, L.tA, L.tB, at));
       UIC_TRY(uic_colsum_launch(dt, L.d_patt, NR, A, A, G->ctx2att_b, L.colscratch, L.colscratch_floats, s));
     }
     // d att' = (the attention's own share, in L.d_att) + d p_att W_ctx2att; without BatchNorm behind it and with one feature row
@@ -1586,11 +1574,11 @@ struct Step {
     if (ones_ok && D % 128 == 0 && NRa % 64 == 0) {
       const UicGemmTnSeg segs[2] = {{att_in, D, D}, {L.ones_blk, 128, 128}};
       const WDest dd[2] = {{G->att_w, D, 0, D}, {G->att_b, 1, D, 1}};
-      UIC_TRY(wgrad_group(L.slab, L.d_pre, H, H, segs, 2, NRa, dd, 2, s, false, L.tA, L.tB));
+      UIC_TRY(wgrad_group(L.slab, L.d_pre, H, H, segs, 2, NRa, dd, 2, s, false, L.tA, L.tB, at));
     } else {
       const UicGemmTnSeg seg{att_in, D, D};
       const WDest d1{G->att_w, D, 0, D};
-      UIC_TRY(wgrad_group(L.slab, L.d_pre, H, H, &seg, 1, NRa, &d1, 1, s, false, L.tA, L.tB));
+      UIC_TRY(wgrad_group(L.slab, L.d_pre, H, H, &seg, 1, NRa, &d1, 1, s, false, L.tA, L.tB, at));
       UIC_TRY(uic_colsum_launch(dt, L.d_pre, NRa, H, H, G->att_b, L.colscratch, L.colscratch_floats, s));
     }
     if (b->d_att_feats) {  // optional: d att_feats = d_pre W_att  (one row per image region; d_pre is already folded over seq_per_img)
@@ -1718,7 +1706,7 @@ int uic_topdown_backward(const uic_topdown_dims* d, const uic_topdown_weights* w
     UIC_TRY(uic_logsoftmax_bwd_launch(st.dt, st.L.dlogits, st.Meff, st.V1, st.V1p, st.N, dlogprobs, (size_t)st.V1,
                                       (size_t)d->T * st.V1, logprobs, s));
   UIC_TRY(st.dh_rows(0, t_run, s));
-  UIC_TRY(st.logit_weight_grads(s));
+  UIC_TRY(st.logit_weight_grads(s, UIC_WG_ALONE));
   UIC_TRY(st.bwd_begin(s));
   UIC_TRY(st.bwd_steps(0, t_run, s));
   return st.bwd_epilogue(s);
@@ -1740,7 +1728,6 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   UIC_TRY(get_side(&ss));
   hipStream_t s2 = ss->stream;
   hipStream_t s3 = ss->stream3;
-  hipStream_t s4 = ss->stream4;
   Step st;
   st.init(d, w, derived, b, t_run, training, seed, workspace, G);
   // The fused step's BPTT is always the launch chain: the persistent BPTT kernel holds every CU, which serialises the side
@@ -1757,21 +1744,15 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   // behind the logit layer (round 4's order), instead of stream 3.
   const bool comm = (d->recurrence & UIC_REC_COMM_STREAM) != 0;
   const int CH = WG_CHUNK;                            // decode steps per hand-off to the side stream
-  // chunk c = decode steps [cb[c], cb[c + 1]).  Default: chunks of CH from step 0 (the last one -- the one the BPTT loop starts
-  // from -- is t_run % CH steps long: ONE at the reference's 17 steps).  UIC_KNOB_SHORT_FIRST (measurement knob): the FIRST chunk is
-  // one step too -- the BPTT loop ends on it, so that all but 1/t_run of the recurrent weight gradients is done when the loop ends.
+  // chunk c = decode steps [cb[c], cb[c + 1]): chunks of CH from step 0 (the last one -- the one the BPTT loop starts from -- is
+  // t_run % CH steps long: ONE at the reference's 17 steps)
   int cb[MAX_CHUNKS + 1];
   int nchunk = 0;
   {
     UIC_REQUIRE((t_run + CH - 1) / CH + 2 <= MAX_CHUNKS, "xe_train_step: too many decode steps (%d)", t_run);
-    int t = 0;
     cb[0] = 0;
-    const bool short_first = (d->recurrence & UIC_KNOB_SHORT_FIRST) && !early && t_run > CH + 1;
-    if (short_first) { cb[++nchunk] = 1; t = 1; }
-    while (t < t_run) {
-      int len = CH < t_run - t ? CH : t_run - t;
-      if (short_first && t_run - t > 1 && t + len == t_run) len = t_run - t - 1;   // keep the loop's first chunk short too
-      t += len;
+    for (int t = 0; t < t_run;) {
+      t += CH < t_run - t ? CH : t_run - t;
       cb[++nchunk] = t;
     }
   }
@@ -1793,9 +1774,7 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   // (the live list, when the caller left it to the library: on the side stream ahead of its prologue branch, whose event the main
   // stream waits for before the recurrence -- every logit chunk on either stream is ordered behind it)
   // (the whole recurrence as one launch of the weight-stationary kernel: it fills the compact operand itself)
-#ifndef UIC_NO_FUSED_GATHER          // (A/B builds: the gather launches)
   st.fused_gather = st.compact && st.build_live && !(training & 4) && st.persist_ok() && st.dt == UIC_BF16;
-#endif
   if (st.compact && st.build_live) UIC_TRY(st.live_build((training & 4) ? s : s2));
   else if (b->grad_scale) UIC_TRY(st.len_build((training & 4) ? s : s2));
   // (not for a plain masked step without counts: it stays bit-equal to the three separate API calls, whose backward pass sums over
@@ -1873,12 +1852,10 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   // side: logit-layer weight gradients + loss reduction, beside the BPTT loop
   // (weight-gradient GEMMs that run beside the BPTT loop keep the 2-stage kernel: the 4-stage ring's 128 KB of LDS would
   // keep the loop's 74-KB workgroups off its CUs -- measured 3.89 -> 3.99 ms)
-  g_uic_tn_ring_off = 1;
-  g_uic_knobs = d->recurrence & UIC_KNOB_MASK;
   // (data-parallel order: the chunks' gradients share the side stream with the logit layer, where the 128 x 128 kernel's short
   // launches serve the stream's latency better than 56-workgroup ones -- 3.84 vs 3.99 ms per step beside the stand-in exchange)
-  if (comm) g_uic_knobs |= UIC_KNOB_CHUNK_TN128;
-  UIC_TRY(st.logit_weight_grads(s2, true));
+  const UicWgPlace beside = comm ? UIC_WG_BESIDE_TN128 : UIC_WG_BESIDE;
+  UIC_TRY(st.logit_weight_grads(s2, beside));
   UIC_TRY(uic_reduce_sum_launch(st.L.row_loss, st.compact ? (size_t)st.live_total() : (size_t)t_run * d->N, 0.f, inv, loss_out, s2));
   if (den_out) UIC_TRY(uic_copy_launch(den_out, st.L.scalars, 4, s2));
   UIC_HIP(hipEventRecord(ss->ev_logit, s2));          // gradient group 0 (logit layer) final: its exchange can start now
@@ -1913,33 +1890,24 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
     if (early) {
       UIC_HIP(hipStreamWaitEvent(s2, ss->ev_main[c], 0));
       UIC_HIP(hipStreamWaitEvent(s3, ss->ev_main[c], 0));
-      UIC_TRY(st.wgrad_chunk(t0, t1, c == nchunk - 1, s2, s3));
+      UIC_TRY(st.wgrad_chunk(t0, t1, c == nchunk - 1, beside, s2, false, s3));
       if (c == 1) UIC_TRY(st.embed_grad(1, s2));      // d xt of steps [CH, t_run) is complete: their share of the embedding table
     } else if (comm) {
       UIC_HIP(hipStreamWaitEvent(s2, ss->ev_main[c], 0));
-      UIC_TRY(st.wgrad_chunk(t0, t1, c == nchunk - 1, s2));
+      UIC_TRY(st.wgrad_chunk(t0, t1, c == nchunk - 1, beside, s2, false));
     } else {
-      // default order: the chunk's two independent shares on streams 3 and 4 (the 256 x 256 weight-gradient kernel runs a share on
-      // ~60 CUs: side by side, and beside the side stream's logit layer, they leave the BPTT chain most of the chip), the side
-      // stream stays with the logit layer
-      // ... one chunk after the other on stream 3 while the loop runs (two streams of them slow the chain down again: 3.15 vs
-      // 3.08 ms, profiles/r05_v1_ab_knobs.txt); the LAST chunk's shares, which start when the loop is over, side by side
-      const bool two = false;      // (a fourth stream is not worth having: see get_side)
-      if (two && !(g_uic_knobs & UIC_KNOB_TWO_WG_STREAMS) && nchunk > 1) {
-        // (the att_lstm / h2att share moves to stream 4 for this chunk: it accumulates into what stream 3's chunks wrote)
-        UIC_HIP(hipEventRecord(ss->ev_s3, s3));
-        UIC_HIP(hipStreamWaitEvent(s4, ss->ev_s3, 0));
-      }
+      // default order: the chunks' weight gradients on stream 3, one chunk after the other, both shares of a chunk in turn (the
+      // 256 x 256 weight-gradient kernel runs a share on ~60 CUs: beside the side stream's logit layer they leave the BPTT chain
+      // most of the chip; two streams of them slow the chain down again: 3.15 vs 3.08 ms, profiles/r05_v1_ab_knobs.txt), the side
+      // stream stays with the logit layer.  The LAST chunk's, which start when the loop is over, are dispatched as alone on the chip.
       UIC_HIP(hipStreamWaitEvent(s3, ss->ev_main[c], 0));
-      if (two) UIC_HIP(hipStreamWaitEvent(s4, ss->ev_main[c], 0));
-      if (c == 0 && !(g_uic_knobs & UIC_KNOB_LAST_BESIDE)) g_uic_tn_ring_off = 0;
-      UIC_TRY(st.wgrad_chunk(t0, t1, c == nchunk - 1, s3, two ? s4 : s3, true));
+      UIC_TRY(st.wgrad_chunk(t0, t1, c == nchunk - 1, c == 0 ? UIC_WG_ALONE : beside, s3, true));
     }
   }
   if (early) {
     // side: what completes att_lstm.weight_ih and the embedding table comes first, so that the two big tensors of the early
     // group are final with gradient group 1 (the fc_embed chain and the bias sums -- ~4 MB -- follow)
-    UIC_TRY(st.fc_cols_grad(s2, st.L.slab2, st.L.tSA, st.L.tSB));
+    UIC_TRY(st.fc_cols_grad(s2, st.L.slab2, st.L.tSA, st.L.tSB, beside));
     UIC_TRY(st.embed_grad(0, s2));
     UIC_HIP(hipEventRecord(ss->ev_embed, s2));
     ss->embed_recorded = true;
@@ -1949,37 +1917,31 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
     if (tail3) {   // (round 4's tail: what completes att_lstm.weight_ih and the embedding table on stream 3 beside the last chunk's gradients)
       UIC_HIP(hipStreamWaitEvent(s3, ss->ev_main[0], 0));
       UIC_HIP(hipStreamWaitEvent(s3, ss->ev_prep, 0));
-      UIC_TRY(st.fc_cols_grad(s3, st.L.slab3, st.L.tTA, st.L.tTB));
+      UIC_TRY(st.fc_cols_grad(s3, st.L.slab3, st.L.tTA, st.L.tTB, beside));
       UIC_TRY(st.embed_grad(0, s3));
       UIC_HIP(hipEventRecord(ss->ev_s3, s3));
       UIC_HIP(hipEventRecord(ss->ev_embed, s3));
       ss->embed_recorded = true;
     }
-  } else {
-    // the recurrent weight gradients are complete when both shares of the last chunk are (joined on stream 3)
-    UIC_HIP(hipEventRecord(ss->ev_s4, s4));
-    UIC_HIP(hipStreamWaitEvent(s3, ss->ev_s4, 0));
-    if (tail3) {
-      UIC_HIP(hipStreamWaitEvent(s2, ss->ev_main[0], 0));   // the BPTT loop is through: dG1 of every step exists
-      UIC_TRY(st.fc_cols_grad(s2, st.L.slab2, st.L.tSA, st.L.tSB));
-      UIC_TRY(st.embed_grad(0, s2));
-      UIC_HIP(hipEventRecord(ss->ev_embed, s2));
-      ss->embed_recorded = true;
-    }
+  } else if (tail3) {
+    UIC_HIP(hipStreamWaitEvent(s2, ss->ev_main[0], 0));     // the BPTT loop is through: dG1 of every step exists
+    UIC_TRY(st.fc_cols_grad(s2, st.L.slab2, st.L.tSA, st.L.tSB, UIC_WG_ALONE));
+    UIC_TRY(st.embed_grad(0, s2));
+    UIC_HIP(hipEventRecord(ss->ev_embed, s2));
+    ss->embed_recorded = true;
   }
   // side: the rest of the early gradient group (LSTM / h2att biases, embedding, fc_embed); main: the late group
   // (attention accumulation, ctx2att, att_embed).  ev_early: the early group, the logit layer and the loss are final.
-  g_uic_tn_ring_off = 0;
   UIC_MARK(5, s);                                     // main: BPTT done
   hipStream_t s_lstm = (early || comm) ? s2 : s3;
   UIC_HIP(hipEventRecord(ss->ev_lstm, s_lstm));       // gradient group 1 final (uic_topdown_grad_ready_wait)
   UIC_MARK(6, s_lstm);                                // side: recurrent weight gradients done
-  UIC_TRY(st.bwd_epilogue_late(s, true));             // (enqueued first: it is the longer of the two tails)
+  UIC_TRY(st.bwd_epilogue_late(s, UIC_WG_ALONE, true));   // (enqueued first: it is the longer of the two tails)
   UIC_MARK(7, s);
   if (!early && !tail3) UIC_HIP(hipStreamWaitEvent(s2, ss->ev_main[0], 0));
   if (comm && tail3) UIC_HIP(hipStreamWaitEvent(s2, ss->ev_s3, 0));      // (d fc' below reads the dGfc that fc_cols_grad left)
   const bool chunks_elsewhere = !early && !comm;      // the chunks' weight (and bias) gradients were made on stream 3
-  UIC_TRY(st.bwd_epilogue_early(s2, true, true, early || tail3, !chunks_elsewhere));
+  UIC_TRY(st.bwd_epilogue_early(s2, UIC_WG_ALONE, true, true, early || tail3, !chunks_elsewhere));
   if (chunks_elsewhere) {
     UIC_HIP(hipStreamWaitEvent(s2, ss->ev_lstm, 0));  // the early group includes them; bias_hh = bias_ih needs the bias columns
     UIC_TRY(st.bias_hh_copies(s2));

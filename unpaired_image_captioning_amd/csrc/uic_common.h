@@ -141,21 +141,6 @@ __device__ __forceinline__ float uic_wave_max(float v) {
 }
 #endif  // __HIPCC__
 
-// gemm_tn.hip: set (by the calling host thread, around its launches) to keep uic_gemm_tn_launch on the 2-stage kernel even
-// for grids of at most one workgroup per CU -- for launches that must share CUs with another stream's LDS-heavy workgroups
-extern thread_local int g_uic_tn_ring_off;
-// measurement knobs of the fused training step (bits 8-15 of uic_topdown_dims.recurrence; tools/ab_knobs.py): NOT part of the
-// interface, every bit off = the shipped behaviour
-extern thread_local int g_uic_knobs;
-#define UIC_KNOB_TWO_WG_STREAMS 0x100  // every chunk's two weight-gradient shares on TWO extra streams (default: one; two for the last chunk only)
-#define UIC_KNOB_CHUNK_TN128 0x200     // beside the BPTT chain: the LSTM / h2att chunk gradients on the 128 x 128 kernel
-#define UIC_KNOB_LOGIT_TN128 0x400     // beside the BPTT chain: the logit weight gradient on the 128 x 128 kernel
-#define UIC_KNOB_CHUNK_SK2 0x800       // beside the BPTT chain: two K slices for the chunk gradients
-#define UIC_KNOB_LAST_BESIDE 0x1000    // the last chunk's gradients (after the loop) dispatched like the others (default: as if alone on the chip)
-#define UIC_KNOB_LAST_ONE_STREAM 0x2000 // the last chunk's two shares on one stream
-#define UIC_KNOB_SHORT_FIRST 0x4000     // the first decode step is a chunk of its own (the BPTT loop ends on it): see uic_topdown_xe_train_step
-#define UIC_KNOB_MASK 0xff00
-
 // ---------------------------------------------------------------- GEMM (gemm.hip)
 #define UIC_GEMM_RELU 1      // v = max(v, 0)
 #define UIC_GEMM_ACCUM 2     // C += v
@@ -253,7 +238,15 @@ struct UicGemmTnParams {
 struct UicSlabDest { float* C; int ldc, col0, ncols; };
 int uic_splitk_reduce_multi_launch(const float* slab, int splitk, int M, int N, const UicSlabDest* dst, int nd, int accumulate, hipStream_t s);
 bool uic_gemm_tn_eligible(const UicGemmTnParams& p);
-int uic_gemm_tn_launch(const UicGemmTnParams& p, hipStream_t s);
+// Where a weight-gradient launch runs (wgrad_multi / wgrad_tn / wgrad_group of uic_host.h, uic_gemm_tn_launch): it decides the
+// kernel and the split over K, so the caller passes it with every call.
+enum UicWgPlace {
+  UIC_WG_ALONE = 0,          // alone on the chip: split over K until ~one workgroup per CU; such grids take the 4-stage TN kernel
+  UIC_WG_BESIDE = 1,         // beside the fused training step's BPTT chain: few workgroups, 2-stage TN kernel only (the 4-stage
+                             // one's 128 KB of LDS would keep the chain's workgroups off their CUs)
+  UIC_WG_BESIDE_TN128 = 2,   // the same, with every problem of K <= 8192 (all but the logit layer's) on the 128 x 128 kernel
+};
+int uic_gemm_tn_launch(const UicGemmTnParams& p, hipStream_t s, UicWgPlace at);
 // the 256 x 256 ping-pong form (gemm_tn_pp.hip): whole pairs of 64-row K tiles per split-K slice
 bool uic_gemm_tnpp_eligible(const UicGemmTnParams& p);
 int uic_gemm_tnpp_launch(const UicGemmTnParams& p, hipStream_t s);

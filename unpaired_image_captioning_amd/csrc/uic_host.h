@@ -44,7 +44,7 @@ struct WDest { float* C; int ldc; int col0; int ncols; };
 // instead of dst (entries outside [0, rows->limit) dropped) and sets rows->used; the direct path ignores it and writes dst
 struct WRows { const int* map; int n; int limit; float* C; int ldc; bool used; };
 inline int wgrad_multi(float* slab, size_t slab_bytes, int dt, const void* left, int lrows, const void* right, int rrows, int K,
-                const WDest* dst, int nd, hipStream_t s, bool accumulate = false, WRows* rows = nullptr) {
+                const WDest* dst, int nd, hipStream_t s, bool accumulate = false, WRows* rows = nullptr, UicWgPlace at = UIC_WG_ALONE) {
   if (rows) rows->used = false;
   const long blocks = (long)((lrows + 127) / 128) * ((rrows + 127) / 128);
   if (uic_gemm_glds_eligible(dt, K) && lrows >= 128 && rrows >= 128) {
@@ -54,7 +54,7 @@ inline int wgrad_multi(float* slab, size_t slab_bytes, int dt, const void* left,
     if (sk > nt / 4) sk = nt / 4 > 0 ? nt / 4 : 1;
     // alone on the chip with a long reduction (the NMT generator's d out: 64 tiles x 782 rounds): one workgroup per CU, so that the
     // launch takes the 128 x 128 kernel's three-buffer ring (a K round then costs 0.3 us instead of 0.8: 87 -> 65 us)
-    if (g_uic_tn_ring_off == 0 && blocks <= 128 && nt >= 128) {
+    if (at == UIC_WG_ALONE && blocks <= 128 && nt >= 128) {
       int one_per_cu = (int)(256 / blocks);
       if (one_per_cu > 8) one_per_cu = 8;
       if (one_per_cu >= 2 && nt / one_per_cu >= 32) sk = one_per_cu;
@@ -65,13 +65,11 @@ inline int wgrad_multi(float* slab, size_t slab_bytes, int dt, const void* left,
       add_seg(g, left, K, right, K, K);
       g.splitk = sk; g.slab = slab;
       UIC_TRY(uic_gemm_launch(g, s));
-#ifndef UIC_NO_REDUCE_ROWS        // (A/B builds: the separate scatter launch)
       if (rows && nd == 1 && !accumulate && dst[0].col0 == 0 && dst[0].ncols == rrows && rows->n <= lrows &&
           uic_splitk_reduce_rows_ok(slab, lrows, rrows, rows->C, rows->ldc)) {
         rows->used = true;
         return uic_splitk_reduce_rows_launch(slab, sk, lrows, rrows, rows->map, rows->n, rows->limit, rows->C, rows->ldc, s);
       }
-#endif
       for (int i = 0; i < nd; ++i)
         UIC_TRY(uic_splitk_reduce_launch(slab, sk, lrows, rrows, dst[i].col0, dst[i].ncols, dst[i].C, dst[i].ldc, s, accumulate ? 1 : 0));
       return UIC_OK;
@@ -92,10 +90,10 @@ inline int wgrad_multi(float* slab, size_t slab_bytes, int dt, const void* left,
 //
 // Two kernels.  The 256 x 256 ping-pong form takes every problem with whole pairs of K tiles and >= 1024 reduction rows: it
 // needs a quarter of the 128 x 128 kernel's workgroups for the same flops and half its LDS traffic.  How many workgroups a
-// launch should have depends on where it runs (g_uic_tn_ring_off, set by the fused training step around the BPTT loop):
+// launch should have depends on where it runs (`at`, passed by the caller):
 //   * beside the BPTT chain (CU-time-bound window): as FEW workgroups as the problem has 256 x 256 tiles -- the chain's kernels
 //     need the other CUs --, split over K only until ~48 CUs work on it;
-//   * alone on the chip (the step's tail): split over K until one workgroup per CU, slices of >= 4 K tiles.
+//   * alone on the chip (the step's tail, every stand-alone call): split over K until one workgroup per CU, slices of >= 4 K tiles.
 // how: UIC_TN_FORCE_* | UIC_TN_SPLITK(n) for measurements and tests (0: the dispatcher's choice).
 // K slices of a 256 x 256 launch.  Cost model fitted to tools/tn_bench.py (profiles/r05_*_tn_bench.txt): one workgroup per CU,
 // so ceil(workgroups / 256) rounds of (K tiles per slice x 1.05 us + 8 us), plus the slab traffic of a split launch (partials
@@ -129,12 +127,9 @@ inline int tnpp_splitk(long tiles, int nt, size_t out_bytes, size_t slab_bytes, 
   return best;
 }
 inline int wgrad_tn(float* slab, size_t slab_bytes, int dt, const void* A, int lda, int lrows, const UicGemmTnSeg* segs, int nseg,
-                    int K, const WDest* dst, int nd, hipStream_t s, bool accumulate, bool* done, int how = 0) {
+                    int K, const WDest* dst, int nd, hipStream_t s, bool accumulate, bool* done, int how = 0, UicWgPlace at = UIC_WG_ALONE) {
   *done = false;
   if (dt != UIC_BF16 || nseg > UIC_GEMM_TN_MAX_SEG) return UIC_OK;
-#ifdef UIC_TNPP_OFF       // (A/B builds: tools/build_variant.sh)
-  if (!(how & UIC_TN_FORCE_256)) how |= UIC_TN_FORCE_128;
-#endif
   UicGemmTnParams p;
   memset(&p, 0, sizeof(p));
   p.A = A; p.lda = lda; p.M = lrows; p.K = K; p.nseg = nseg;
@@ -160,20 +155,15 @@ inline int wgrad_tn(float* slab, size_t slab_bytes, int dt, const void* A, int l
   };
   // ---- the 256 x 256 ping-pong kernel
   if (!(how & UIC_TN_FORCE_128)) {
+    const bool beside = at != UIC_WG_ALONE;
     const long t256 = (long)((lrows + 255) / 256) * ((rrows + 255) / 256);
-    int sk = sk_forced ? sk_forced : tnpp_splitk(t256, nt, out_bytes, slab_bytes, g_uic_tn_ring_off != 0);
+    const int sk = sk_forced ? sk_forced : tnpp_splitk(t256, nt, out_bytes, slab_bytes, beside);
     UicGemmTnParams q = p;
     q.splitk = sk; q.slab = slab;
     // beside the BPTT chain every problem with a real K loop; alone on the chip the 128 x 128 kernel's many small workgroups
     // finish a small problem sooner (tools/tn_bench.py: LSTM chunk 31 vs 45 us, ctx2att 36 vs 45; logit 181 vs 146, att_embed 79 vs 70)
-    const bool beside = g_uic_tn_ring_off != 0;
     bool wanted = (how & UIC_TN_FORCE_256) || (lrows >= 256 && (beside ? K >= 1024 : 2.0 * lrows * rrows * K >= 3.0e10));
-    if (beside && !(how & UIC_TN_FORCE_256)) {
-      const bool logit = K > 8192;
-      if ((g_uic_knobs & UIC_KNOB_CHUNK_TN128) && !logit) wanted = false;
-      if ((g_uic_knobs & UIC_KNOB_LOGIT_TN128) && logit) wanted = false;
-      if ((g_uic_knobs & UIC_KNOB_CHUNK_SK2) && !logit && !sk_forced && sk == 1 && nt % 4 == 0) { sk = 2; q.splitk = 2; }
-    }
+    if (at == UIC_WG_BESIDE_TN128 && !(how & UIC_TN_FORCE_256) && K <= 8192) wanted = false;
     const bool direct = sk == 1 && nd <= UIC_GEMM_TN_MAX_SEG;
     if (direct) { q.ndst = nd; q.accumulate = accumulate ? 1 : 0; for (int i = 0; i < nd; ++i) { q.dst[i].C = dst[i].C; q.dst[i].ldc = dst[i].ldc; q.dst[i].col0 = dst[i].col0; q.dst[i].ncols = dst[i].ncols; } }
     const bool fits = direct || (size_t)sk * out_bytes <= slab_bytes;
@@ -197,10 +187,10 @@ inline int wgrad_tn(float* slab, size_t slab_bytes, int dt, const void* A, int l
   p.splitk = sk; p.slab = slab;
   if (sk == 1 && nd <= UIC_GEMM_TN_MAX_SEG) {
     set_dst();
-    UIC_TRY(uic_gemm_tn_launch(p, s));
+    UIC_TRY(uic_gemm_tn_launch(p, s, at));
   } else {
     if ((size_t)sk * out_bytes > slab_bytes) return UIC_OK;
-    UIC_TRY(uic_gemm_tn_launch(p, s));
+    UIC_TRY(uic_gemm_tn_launch(p, s, at));
     UIC_TRY(reduce(sk));
   }
   *done = true;
@@ -211,9 +201,9 @@ inline int wgrad_tn(float* slab, size_t slab_bytes, int dt, const void* A, int l
 // bf16 on eligible shapes: gemm_tn.hip reads both operands as they lie (transposing LDS reads).  Otherwise (f32 parity path,
 // odd sizes): transposed copies into tA [lrows, rows^8] / tB [cols, rows^8] and the NT kernels (wgrad_multi).
 inline int wgrad_group(float* slab, size_t slab_bytes, int dt, const void* A, int lda, int lrows, const UicGemmTnSeg* segs, int nseg,
-                       int rows, const WDest* dst, int nd, hipStream_t s, bool accumulate, void* tA, void* tB) {
+                       int rows, const WDest* dst, int nd, hipStream_t s, bool accumulate, void* tA, void* tB, UicWgPlace at = UIC_WG_ALONE) {
   bool done = false;
-  UIC_TRY(wgrad_tn(slab, slab_bytes, dt, A, lda, lrows, segs, nseg, rows, dst, nd, s, accumulate, &done));
+  UIC_TRY(wgrad_tn(slab, slab_bytes, dt, A, lda, lrows, segs, nseg, rows, dst, nd, s, accumulate, &done, 0, at));
   if (done) return UIC_OK;
   const int Kp = (int)rup8(rows);
   UIC_TRY(uic_transpose_launch(dt, A, rows, lrows, lda, tA, Kp, s));
@@ -222,7 +212,7 @@ inline int wgrad_group(float* slab, size_t slab_bytes, int dt, const void* A, in
     UIC_TRY(uic_transpose_launch(dt, segs[i].B, rows, segs[i].ncols, segs[i].ldb, offw(tB, (size_t)col * Kp, dt), Kp, s));
     col += segs[i].ncols;
   }
-  return wgrad_multi(slab, slab_bytes, dt, tA, lrows, tB, col, Kp, dst, nd, s, accumulate);
+  return wgrad_multi(slab, slab_bytes, dt, tA, lrows, tB, col, Kp, dst, nd, s, accumulate, nullptr, at);
 }
 
 }  // namespace
