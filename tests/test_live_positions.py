@@ -1,7 +1,12 @@
 """The list of live (step, row) positions (uic_topdown_batch.live_rows / live_count): the fused step's logit layer and criterion
 run over the positions whose mask is not zero only.  LanguageModelCriterion multiplies every other position by zero
 (reference misc/utils.py:62-73), so the step's loss and gradients are the ones of the full computation -- checked here against
-the full computation of the library itself, against the reference's golden vectors and against the CPU oracle."""
+the full computation of the library itself, against the reference's golden vectors and against the CPU oracle.
+The shapes here are small (32 to 160 hidden units: the per-step launch chain) but for one bf16 run at full size against the
+library's own step over all positions.  The oracle comparison of the timed configuration -- 512 hidden units, the persistent
+recurrence kernel and its store of the live hdrop rows into the compact logit operand, training-mode dropout -- is in
+tests/test_gpu_fullsize.py (640 rows) and tests/test_gpu_live_persist.py (row counts, masks and region counts at the edges;
+Trainer.train_device_batch over several steps)."""
 import ctypes as C
 import os
 import subprocess
