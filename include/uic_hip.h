@@ -351,6 +351,39 @@ int uic_topdown_logprobs_state(const uic_topdown_dims* d, const uic_topdown_weig
                                const float* h_in, const float* c_in, int32_t t, int32_t training, uint32_t seed, void* workspace,
                                float* logprobs, float* h_out, float* c_out, void* stream);
 
+/* ---- ensemble of captioners: AttEnsemble (P/models/AttEnsemble.py, eval_ensemble.py:118-129) decodes with the MEAN of its
+ * members' word distributions.  The three calls below take ARRAYS of M <= UIC_ENSEMBLE_MAX per-member pointers (host arrays,
+ * read during the call only). */
+#define UIC_ENSEMBLE_MAX 8
+/* The combination on its own (AttEnsemble.py:53: softmax per member, mean over the members, log):
+ *   out[n, v] = log( (1/M) sum_m softmax(logits[m][n, :])[v] ),   n < N, v < V1,
+ * logits[m] f32 [N, ld[m]], out f32 [N, ld_out], every leading dimension >= V1 and every row backed by its full leading
+ * dimension; columns [V1, ld_out) of out are not written.  out may be one of the logits[m].  f32 arithmetic, evaluated as a
+ * log-sum-exp over the members' log-probs: finite wherever one member's log-prob is, and M = 1 is log_softmax.  A member's
+ * LOG-PROBS are as good an input as its logits (softmax of log-probs is the distribution itself): AttEnsemble.get_logprobs_state
+ * passes what uic_topdown_logprobs_state returned. */
+int uic_ensemble_logprobs(int32_t M, int32_t N, int32_t V1, const float* const* logits, const int32_t* ld, float* out,
+                          int32_t ld_out, void* stream);
+/* AttModel._sample with beam_size = 1 over the ensemble, eval mode (the reference ensemble only runs under eval()): arguments
+ * as uic_topdown_sample, per member where they are arrays.  The members share N, V1, R, T and seq_per_img; H, A, E, D, use_bn,
+ * logit_layers and dtype are each member's own (its dims, derived copies and workspace) -- anything else is an argument error.
+ * Per decode step and on the one stream: every member's decode step, the combination into member 0's step logits, the single
+ * model's sampling kernel once (greedy, temperature multinomial, decoding_constraint, forced); every member reads the chosen
+ * token from member 0's workspace.  ALWAYS the per-step launch chain: the one-launch persistent decode keeps ONE model's
+ * weights resident across the steps and has no place for M of them, whatever d[m]->recurrence says. */
+int uic_topdown_ensemble_sample(int32_t M, const uic_topdown_dims* const* d, const uic_topdown_weights* const* w,
+                                const void* const* derived, const uic_topdown_batch* const* batch, int32_t L, int32_t sample_max,
+                                float temperature, int32_t decoding_constraint, uint32_t seed, const int64_t* forced,
+                                void* const* workspace, int64_t* seq, float* seq_logp, void* stream);
+/* AttEnsemble._sample_beam + beam_search with group_size = 1 (AttEnsemble.py:69-98,100-244): uic_topdown_sample_beam with the
+ * ensemble's log-probs.  Per step: every member's decode step, the combination, ONE beam step on member 0's beam buffers, every
+ * member's four state tensors re-threaded to the shared surviving parents.  uic_topdown_beam_done_lists(d[0], workspace[0], ...)
+ * right after it returns the done list. */
+int uic_topdown_ensemble_sample_beam(int32_t M, const uic_topdown_dims* const* d, const uic_topdown_weights* const* w,
+                                     const void* const* derived, const uic_topdown_batch* const* batch, int32_t L, int32_t beam_size,
+                                     int32_t decoding_constraint, int32_t max_ppl, void* const* workspace, int64_t* seq,
+                                     float* seq_logp, void* stream);
+
 /* Address of a named activation inside the workspace (tests / debugging); NULL if unknown.
  * Names: fc_embed att_embed p_att e_att xt gx h_att h_lang c_att c_lang att_h alpha ctx logits dlogits ...  (e_att, bf16 workspaces
  * only: e^{2 p_att} of the rounded p_att, what the persistent training recurrence's attention reads -- tanh(p + h) = 1 - 2 / (1 + e^{2p} e^{2h})) */

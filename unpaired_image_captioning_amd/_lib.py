@@ -30,6 +30,7 @@ STEP_MARKS = 11          # UIC_STEP_MARKS
 
 
 MAX_LOGIT_LAYERS = 4
+ENSEMBLE_MAX = 8        # UIC_ENSEMBLE_MAX
 SITE_LOGIT_H0 = 8       # + hidden logit block
 
 
@@ -266,6 +267,12 @@ _SIGS = {
     "uic_topdown_sample_train": (C.c_int, [C.POINTER(Dims), C.POINTER(Weights), C.c_void_p, C.POINTER(Batch), C.c_int32,
                                      C.c_int32, C.c_float, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p,
                                      C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uic_ensemble_logprobs": (C.c_int, [C.c_int32] * 3 + [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.c_void_p, C.c_int32, C.c_void_p]),
+    "uic_topdown_ensemble_sample": (C.c_int, [C.c_int32] + [C.POINTER(C.c_void_p)] * 4 + [C.c_int32, C.c_int32, C.c_float, C.c_int32,
+                                                                                         C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p),
+                                                                                         C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uic_topdown_ensemble_sample_beam": (C.c_int, [C.c_int32] + [C.POINTER(C.c_void_p)] * 4 + [C.c_int32] * 4 +
+                                         [C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p]),
     "uic_fc_workspace_bytes": (C.c_size_t, [C.POINTER(FcDims)]),
     "uic_fc_forward": (C.c_int, [C.POINTER(FcDims), C.POINTER(FcWeights), C.POINTER(Batch), C.c_int32, C.c_int32, C.c_uint32,
                                  C.c_void_p, C.c_void_p, C.c_void_p]),

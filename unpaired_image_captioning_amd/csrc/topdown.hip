@@ -2223,3 +2223,152 @@ int uic_topdown_sample_beam(const uic_topdown_dims* d, const uic_topdown_weights
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- ensemble of M captioners (P/models/AttEnsemble.py)
+// Every member keeps its own dims / weights / derived copies / workspace and runs the decode step of the single-model chain on
+// the caller's stream; ensemble_logmean_kernel (ensemble.hip) then folds the M rows of step logits into member 0's, and the
+// single model's sampling / beam kernels go on from there as if member 0 had produced them.  The chosen token needs no copy:
+// every member's embedding lookup reads member 0's `s_it`.
+namespace {
+
+// L is make_layout() of the member's own workspace with ONE field patched: L.s_it of every member is member 0's.  decode_step
+// reads the input token from L.s_it only (its embedding lookup; the ensemble path never passes xt_ready), and the sampling / beam
+// kernels write it to member 0's: the members' own s_it buffers stay unused, and nothing else of a Layout may be shared.
+struct Member {
+  const uic_topdown_dims* d; const uic_topdown_weights* w; const uic_topdown_batch* b;
+  Derived dv; Layout L;
+};
+
+int ensemble_members(const char* what, int M, const uic_topdown_dims* const* d, const uic_topdown_weights* const* w, const void* const* derived,
+                     const uic_topdown_batch* const* b, void* const* workspace, int Lsteps, Member* mem) {
+  UIC_REQUIRE(M >= 1 && M <= UIC_ENSEMBLE_MAX, "%s: %d members outside [1, %d]", what, M, UIC_ENSEMBLE_MAX);
+  UIC_REQUIRE(d && w && derived && b && workspace, "%s: null pointer", what);
+  for (int m = 0; m < M; ++m) {
+    UIC_REQUIRE(d[m] && w[m] && derived[m] && b[m] && workspace[m], "%s: null pointer (member %d)", what, m);
+    UIC_TRY(check_dims(d[m]));
+    UIC_REQUIRE(b[m]->fc_feats && b[m]->att_feats, "%s: member %d's batch needs fc_feats and att_feats", what, m);
+    UIC_REQUIRE(d[m]->N == d[0]->N && d[m]->V1 == d[0]->V1 && d[m]->R == d[0]->R && d[m]->T == d[0]->T,
+                "%s: member %d has N=%d V1=%d R=%d T=%d, member 0 N=%d V1=%d R=%d T=%d (the members must share rows, vocabulary, regions and length)",
+                what, m, d[m]->N, d[m]->V1, d[m]->R, d[m]->T, d[0]->N, d[0]->V1, d[0]->R, d[0]->T);
+    UIC_REQUIRE((d[m]->seq_per_img > 1 ? d[m]->seq_per_img : 1) == (d[0]->seq_per_img > 1 ? d[0]->seq_per_img : 1),
+                "%s: member %d replicates every image %d times, member 0 %d times", what, m, d[m]->seq_per_img, d[0]->seq_per_img);
+    for (int k = 0; k < m; ++k)
+      UIC_REQUIRE(workspace[k] != workspace[m], "%s: members %d and %d share a workspace", what, k, m);
+  }
+  UIC_REQUIRE(Lsteps >= 1 && Lsteps <= d[0]->T, "%s: L=%d outside [1,%d]", what, Lsteps, d[0]->T);
+  for (int m = 0; m < M; ++m) {
+    mem[m].d = d[m]; mem[m].w = w[m]; mem[m].b = b[m];
+    mem[m].L = make_layout(*d[m], workspace[m]);
+    mem[m].dv = make_derived(*d[m], w[m], (void*)derived[m]);
+    mem[m].L.s_it = mem[0].L.s_it;
+  }
+  return UIC_OK;
+}
+
+// eval-mode features and the zero initial state of every member, <bos> as the first input
+int ensemble_begin(int M, Member* mem, hipStream_t s) {
+  for (int m = 0; m < M; ++m) {
+    const void *fc_in, *att_in;
+    UIC_TRY(prepare_features(*mem[m].d, mem[m].w, mem[m].dv, mem[m].b, mem[m].L, 0, 0.f, 0, &fc_in, &att_in, s));
+  }
+  UIC_TRY(wait_refresh(s));      // (one side stream made every member's copies, in order: its last event covers them all)
+  for (int m = 0; m < M; ++m) {
+    const Layout& L = mem[m].L;
+    const size_t NH = (size_t)mem[m].d->N * mem[m].d->H, S = uic_dtype_size(mem[m].d->dtype);
+    UIC_TRY(uic_zero4_launch(L.s_h_att[0], NH * S, L.s_h_lang[0], NH * S, L.s_c_att[0], NH * 4, L.s_c_lang[0], NH * 4, s));
+  }
+  return uic_fill_launch(mem[0].L.s_it, 0, (size_t)mem[0].d->N * 8, s);
+}
+
+// one get_logprobs_state of the ensemble (AttEnsemble.py:48-55): states slot `cur` -> `nxt`, combined log-probs into member 0's s_logits
+int ensemble_step(int M, const Member* mem, int cur, int nxt, int t, hipStream_t s) {
+  UicEnsembleParams e;
+  memset(&e, 0, sizeof(e));
+  e.M = M; e.N = mem[0].d->N; e.V1 = mem[0].d->V1;
+  for (int m = 0; m < M; ++m) {
+    UIC_TRY(decode_step(*mem[m].d, mem[m].w, mem[m].dv, mem[m].b, mem[m].L, cur, nxt, t, 0.f, 0, s));
+    e.x[m] = mem[m].L.s_logits; e.ld[m] = (int)vpad(e.V1);
+  }
+  e.out = mem[0].L.s_logits; e.ld_out = (int)vpad(e.V1);
+  return uic_ensemble_logmean_launch(e, s);
+}
+
+}  // namespace
+
+extern "C" {
+
+int uic_topdown_ensemble_sample(int32_t M, const uic_topdown_dims* const* d, const uic_topdown_weights* const* w, const void* const* derived,
+                                const uic_topdown_batch* const* b, int32_t Lsteps, int32_t sample_max, float temperature,
+                                int32_t decoding_constraint, uint32_t seed, const int64_t* forced, void* const* workspace,
+                                int64_t* seq, float* seq_logp, void* stream) {
+  Member mem[UIC_ENSEMBLE_MAX];
+  UIC_TRY(ensemble_members("ensemble_sample", M, d, w, derived, b, workspace, Lsteps, mem));
+  UIC_REQUIRE(seq && seq_logp, "ensemble_sample: null pointer");
+  UIC_REQUIRE(temperature > 0.f, "ensemble_sample: temperature must be positive");
+  hipStream_t s = (hipStream_t)stream;
+  const Layout& L0 = mem[0].L;
+  const int N = d[0]->N, V1 = d[0]->V1;
+  bool all_bf16 = true;
+  for (int m = 0; m < M; ++m) all_bf16 = all_bf16 && d[m]->dtype == UIC_BF16;
+  UIC_TRY(ensemble_begin(M, mem, s));
+  UIC_TRY(uic_fill_launch(L0.s_unf, 0, (size_t)N * 4, s));
+  UIC_TRY(uic_fill_launch(L0.s_nunf, 0, (size_t)(d[0]->T + 2) * UIC_NUNF_STRIPES * 4, s));
+  for (int t = 0; t < Lsteps; ++t) {
+    const int cur = t & 1, nxt = cur ^ 1;
+    UIC_TRY(ensemble_step(M, mem, cur, nxt, t, s));
+    UicSampleParams p;
+    memset(&p, 0, sizeof(p));
+    // (the hardware exponential of the bf16 sampling kernel only when no member is an f32 parity model)
+    p.dtype = all_bf16 ? UIC_BF16 : UIC_F32; p.N = N; p.V1 = V1; p.ldv = (int)vpad(V1); p.t = t; p.L = Lsteps;
+    p.logits = L0.s_logits; p.sample_max = sample_max; p.temperature = temperature; p.seed = seed;
+    p.decoding_constraint = decoding_constraint;
+    p.seq = seq; p.seq_logp = seq_logp; p.it = L0.s_it; p.unfinished = L0.s_unf; p.n_unfinished = L0.s_nunf;
+    p.forced = forced;
+    UIC_TRY(uic_sample_step_launch(p, s));
+  }
+  return UIC_OK;
+}
+
+int uic_topdown_ensemble_sample_beam(int32_t M, const uic_topdown_dims* const* d, const uic_topdown_weights* const* w,
+                                     const void* const* derived, const uic_topdown_batch* const* b, int32_t Lsteps, int32_t beam_size,
+                                     int32_t decoding_constraint, int32_t max_ppl, void* const* workspace, int64_t* seq,
+                                     float* seq_logp, void* stream) {
+  Member mem[UIC_ENSEMBLE_MAX];
+  UIC_TRY(ensemble_members("ensemble_sample_beam", M, d, w, derived, b, workspace, Lsteps, mem));
+  UIC_REQUIRE(seq && seq_logp, "ensemble_sample_beam: null pointer");
+  UIC_REQUIRE(beam_size >= 1 && beam_size <= UIC_BEAM_MAX && beam_size <= d[0]->V1, "ensemble_sample_beam: beam_size=%d outside [1, %d]", beam_size, UIC_BEAM_MAX);
+  UIC_REQUIRE(d[0]->N % beam_size == 0, "ensemble_sample_beam: N=%d rows must be images x beam_size=%d (every image replicated beam_size times)", d[0]->N, beam_size);
+  hipStream_t s = (hipStream_t)stream;
+  const Layout& L0 = mem[0].L;
+  const int N = d[0]->N, V1 = d[0]->V1, T = d[0]->T;
+  UIC_TRY(ensemble_begin(M, mem, s));
+  for (int i = 0; i < 2; ++i) {
+    UIC_TRY(uic_fill_launch(L0.bm_seq[i], 0, (size_t)N * T * 8, s));
+    UIC_TRY(uic_fill_launch(L0.bm_lp[i], 0, (size_t)N * T * 4, s));
+  }
+  UIC_TRY(uic_fill_launch(L0.bm_sum, 0, (size_t)N * 4, s));
+  UIC_TRY(uic_fill_launch(L0.bm_done_count, 0, (size_t)N * 4, s));
+  UicBeamParams p;
+  memset(&p, 0, sizeof(p));
+  p.n_img = N / beam_size; p.B = beam_size; p.L = Lsteps; p.V1 = V1; p.ldv = (int)vpad(V1);
+  p.decoding_constraint = decoding_constraint; p.max_ppl = max_ppl;
+  p.logits = L0.s_logits; p.cand_val = L0.bm_cand_val; p.cand_idx = L0.bm_cand_idx;
+  p.beam_seq_hist[0] = L0.bm_seq[0]; p.beam_seq_hist[1] = L0.bm_seq[1]; p.beam_lp_hist[0] = L0.bm_lp[0]; p.beam_lp_hist[1] = L0.bm_lp[1];
+  p.beam_sum = L0.bm_sum; p.parent = L0.bm_parent; p.it = L0.s_it;
+  p.done_count = L0.bm_done_count; p.done_p = L0.bm_done_p; p.done_seq = L0.bm_done_seq; p.done_lp = L0.bm_done_lp;
+  UIC_TRY(ensemble_step(M, mem, 0, 1, 0, s));                  // logprobs after <bos> (AttEnsemble.py:88-89)
+  for (int t = 0; t < Lsteps; ++t) {
+    p.t = t;
+    UIC_TRY(uic_beam_step_launch(p, s));
+    if (t + 1 == Lsteps) break;                                // (the reference's last get_logprobs_state is never used)
+    for (int m = 0; m < M; ++m) {                              // every member's states follow the surviving parents (CaptionModel.py:90-92)
+      const Layout& L = mem[m].L;
+      UIC_TRY(uic_beam_gather_launch(d[m]->dtype, L0.bm_parent, N, beam_size, d[m]->H, L.s_h_att[1], L.s_h_att[0], L.s_h_lang[1], L.s_h_lang[0],
+                                     L.s_c_att[1], L.s_c_att[0], L.s_c_lang[1], L.s_c_lang[0], s));
+    }
+    UIC_TRY(ensemble_step(M, mem, 0, 1, t + 1, s));
+  }
+  return uic_beam_final_launch(p, seq, seq_logp, s);
+}
+
+}  // extern "C"

@@ -691,4 +691,12 @@ int uic_beam_topk_launch(const UicBeamParams& p, hipStream_t s);     // only the
 int uic_beam_gather_launch(int dtype, const int* parent, int rows, int B, int H, const void* h1s, void* h1d, const void* h2s, void* h2d,
                            const float* c1s, float* c1d, const float* c2s, float* c2d, hipStream_t s);
 int uic_beam_final_launch(const UicBeamParams& p, int64_t* seq_out, float* lp_out, hipStream_t s);
+// ---- ensemble of captioners (ensemble.hip): out[n, v] = log mean_m softmax(x_m[n, :])[v], f32; `out` may be one of the x_m
+#define UIC_ENSEMBLE_MAX 8           /* (the same line as in include/uic_hip.h) */
+struct UicEnsembleParams {
+  int M, N, V1;
+  const float* x[UIC_ENSEMBLE_MAX]; int ld[UIC_ENSEMBLE_MAX];   // member m's logits [N, ld[m]]
+  float* out; int ld_out;                                       // [N, ld_out]; columns [V1, ld_out) are not written
+};
+int uic_ensemble_logmean_launch(const UicEnsembleParams& p, hipStream_t s);
 int uic_dropout_mask_launch(float* out, size_t n, float p, unsigned seed, unsigned site, size_t base, hipStream_t s);

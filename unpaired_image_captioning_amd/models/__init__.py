@@ -1,6 +1,7 @@
 """`models.setup(opt)` with the reference's dispatch (P/models/__init__.py:22-58), restricted to
 the architectures on the hot path."""
 from .AttModel import TopDownModel  # noqa: F401
+from .AttEnsemble import AttEnsemble  # noqa: F401
 from .CaptionModel import CaptionModel  # noqa: F401
 from .FCModel_NMT import FCModel_NMT  # noqa: F401
 from . import NMT_Models  # noqa: F401

@@ -418,6 +418,113 @@ class TopDownEngine(object):
         return ws.buf[offset:offset + n * esz].view(dtype).view(*shape)
 
 
+# ---------------------------------------------------------------------- ensemble of captioners (models/AttEnsemble.py)
+class EnsembleCall(object):
+    """The M per-member pointer arrays of the uic_topdown_ensemble_* calls: every member's own engine builds its (dims, weights,
+    derived copies, batch) and checks a workspace out; leaving the block checks the workspaces back in.  Member m reads
+    atts[m] (its own slice of the region features); fc_feats and att_masks are shared."""
+
+    def __init__(self, engines, params, fc, atts, att_masks, N, T, seq_per_img=1):
+        if not 1 <= len(engines) <= _lib.ENSEMBLE_MAX:
+            raise ValueError("an ensemble has 1..%d members, got %d" % (_lib.ENSEMBLE_MAX, len(engines)))
+        self.engines = list(engines)
+        self.M = len(self.engines)
+        self.ws = []
+        self._keep = []
+        self.d, self.w, self.derived, self.b, self.wsp = ((C.c_void_p * self.M)() for _ in range(5))
+        try:
+            for m, (eng, pd, att) in enumerate(zip(self.engines, params, atts)):
+                d = eng.dims(N, att.shape[1], T, seq_per_img)
+                w = eng.refresh(pd, d)
+                ws = eng.checkout(d, fc.device)
+                self.ws.append(ws)
+                b = eng.batch_struct(fc, att, att_masks)
+                self._keep.append((d, w, b))
+                self.d[m], self.w[m], self.b[m] = C.addressof(d), C.addressof(w), C.addressof(b)
+                self.derived[m], self.wsp[m] = ptr(eng._derived), ptr(ws.buf)
+        except Exception:
+            self.release()
+            raise
+
+    def release(self):
+        for eng, ws in zip(self.engines, self.ws):
+            eng.release(ws)
+        self.ws = []
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.release()
+        return False
+
+
+def ensemble_logprobs(logits, out=None):
+    """uic_ensemble_logprobs: log of the mean of softmax(logits[m]) over the members.  logits: M f32 device tensors [N, V1]
+    whose rows may be strided (unit column stride); returns f32 [N, V1]."""
+    lib = _lib.load()
+    logits = list(logits)
+    M = len(logits)
+    if not 1 <= M <= _lib.ENSEMBLE_MAX:
+        raise ValueError("an ensemble has 1..%d members, got %d" % (_lib.ENSEMBLE_MAX, M))
+    N, V1 = logits[0].shape
+    xs, ld = (C.c_void_p * M)(), (C.c_int32 * M)()
+    for m, t in enumerate(logits + ([out] if out is not None else [])):
+        if not t.is_cuda:
+            raise RuntimeError("libuic_hip needs device tensors; got a %s tensor" % t.device)
+        if t.dtype != torch.float32 or tuple(t.shape) != (N, V1) or (V1 > 1 and t.stride(1) != 1) or (N > 1 and t.stride(0) < V1):
+            raise ValueError("ensemble_logprobs: tensor %d must be float32 [%d, %d] with unit column stride" % (m, N, V1))
+        # the kernel reads whole 16-byte groups of a row whose leading dimension is a multiple of 4: the last row needs them too
+        row = t.stride(0) if N > 1 else V1
+        reach = t.storage_offset() + (N - 1) * row + (min(row, (V1 + 3) // 4 * 4) if row % 4 == 0 else V1)
+        if reach * 4 > t.untyped_storage().nbytes():
+            raise ValueError("ensemble_logprobs: the last row of tensor %d is not backed by its leading dimension" % m)
+        if m < M:
+            xs[m], ld[m] = t.data_ptr(), row
+    if out is None:
+        out = torch.empty(N, V1, dtype=torch.float32, device=logits[0].device)
+    check(lib.uic_ensemble_logprobs(M, N, V1, xs, ld, out.data_ptr(), out.stride(0) if N > 1 else V1, stream()), "ensemble_logprobs")
+    return out
+
+
+def ensemble_sample(engines, params, fc, atts, att_masks, L, sample_max=1, temperature=1.0, decoding_constraint=0, seed=0, forced=None,
+                    seq_per_img=1):
+    """AttModel._sample (beam_size = 1) over an ensemble, eval mode: (seq [N, L], log-probs [N, L]).  seq_per_img = S > 1: features
+    come once per image and S captions are decoded per image (rows image * S + j), as TopDownEngine.sample does it."""
+    N = fc.shape[0] * seq_per_img
+    seq = torch.zeros(N, L, dtype=torch.int64, device=fc.device)
+    lp = torch.zeros(N, L, dtype=torch.float32, device=fc.device)
+    with EnsembleCall(engines, params, fc, atts, att_masks, N, L + 1, seq_per_img) as e:
+        check(e.engines[0].lib.uic_topdown_ensemble_sample(e.M, e.d, e.w, e.derived, e.b, L, int(sample_max), float(temperature),
+                                                           int(decoding_constraint), seed & 0xFFFFFFFF, ptr(forced), e.wsp,
+                                                           ptr(seq), ptr(lp), stream()), "ensemble_sample")
+    return seq, lp
+
+
+def ensemble_sample_beam(engines, params, fc, atts, att_masks, L, beam_size, decoding_constraint=0, max_ppl=0, done_lists=False):
+    """TopDownEngine.sample_beam over an ensemble: rows = (image, beam), replicated on the device by every member."""
+    n_img = fc.shape[0]
+    seq = torch.zeros(n_img, L, dtype=torch.int64, device=fc.device)
+    lp = torch.zeros(n_img, L, dtype=torch.float32, device=fc.device)
+    lists = None
+    with EnsembleCall(engines, params, fc, atts, att_masks, n_img * beam_size, L + 1, beam_size) as e:
+        lib = e.engines[0].lib
+        check(lib.uic_topdown_ensemble_sample_beam(e.M, e.d, e.w, e.derived, e.b, L, int(beam_size), int(decoding_constraint),
+                                                   int(max_ppl), e.wsp, ptr(seq), ptr(lp), stream()), "ensemble_sample_beam")
+        if done_lists:
+            LB = L * beam_size
+            cnt = torch.zeros(n_img, dtype=torch.int32, device=fc.device)
+            dp = torch.zeros(n_img, LB, dtype=torch.float32, device=fc.device)
+            dseq = torch.zeros(n_img, LB, L, dtype=torch.int64, device=fc.device)
+            dlp = torch.zeros(n_img, LB, L, dtype=torch.float32, device=fc.device)
+            check(lib.uic_topdown_beam_done_lists(C.byref(e._keep[0][0]), ptr(e.ws[0].buf), L, int(beam_size), ptr(cnt), ptr(dp),
+                                                  ptr(dseq), ptr(dlp), stream()), "beam_done_lists")
+            lists = (cnt, dp, dseq, dlp)
+    if done_lists:
+        return seq, lp, lists
+    return seq, lp
+
+
 def live_counts(masks):
     """Per decode step, the number of positions whose mask is not zero (uic_topdown_batch.live_count): masks [N, T + 1] host
     array (the loader makes it on the host, P/misc/dataloader/dataloader.py:200-203) -> int32 numpy [T]."""
