@@ -652,6 +652,37 @@ int uic_lm_criterion(int32_t N, int32_t T, int32_t V1, const float* logp, const 
 int uic_reward_criterion(int32_t N, int32_t L, const float* logp, const int64_t* seq, const float* reward, float* loss_out,
                          float* dlogp, void* stream);
 
+/* log_softmax over the vocabulary (P/models/AttModel.py:163) fused with the masked NLL (LanguageModelCriterion,
+ * P/misc/criterion.py:143-150) and its gradient -- the criterion launch of every model step here, on its own.  One of five kernels
+ * runs, picked from ldv, dtype, pointer alignment and the outputs asked for; *kernel_id (host, optional) receives which.
+ *   logits  f32 [M, ldv], row m = position t * N + n (m / N = decode step t, m % N = batch row n); every row is backed by its full
+ *           ldv >= V1 floats.  Columns [V1, ldv) are IGNORED whatever they hold (NaN and inf included).
+ *   target  int64, target[n * ld_target + target_col0 + t]; a value outside [0, V1) scores as target 0.   mask (f32) and
+ *           grad_scale (f32, optional) are addressed the same way with their own stride and first column.
+ *   row_loss[m] = -log_softmax(logits[m])[target] * mask   (f32 [M]; needed when target != NULL)
+ *   dlogits (NULL: no gradient) [M, ldv] in `dtype` (f32 / bf16) = (softmax - onehot(target)) * w with w = mask * inv_den[0]
+ *           (inv_den: a DEVICE scalar, 1 / sum(mask)) or, with grad_scale != NULL, w = grad_scale[n, t] (the self-critical weight,
+ *           either sign).  Columns [V1, ldv) are written as zeros.  Needs target and (mask and inv_den, or grad_scale).
+ *   logprobs (optional) f32, logprobs[n * lp_row_stride + t * lp_step_stride + v] = log_softmax(logits[m])[v], v < V1.
+ *   score_stats (optional, device int32[2], ADDED to): [1] += rows whose raw target is != 0, [0] += those whose arg-max (lowest
+ *           index on ties) equals the raw target -- NMT_loss.score (P/misc/criterion.py:175-184); the mask plays no part.
+ *   row_map (optional, device int32[M]): row m of logits / dlogits / row_loss is position row_map[m] (target and mask are read
+ *           at THAT position).  Rows whose entry is outside [0, row_map_limit) -- the -1 padding of a live-position list -- get
+ *           a zero gradient and NO row_loss entry.  Goes with the masked gradient only (no grad_scale, no logprobs).
+ * tests/test_gpu_criterion.py holds every kernel against float64 at the row lengths where the choice changes;
+ * tests/test_gpu_vocab_edges.py runs small models through the other vocabulary-size thresholds of the library. */
+#define UIC_XE_GENERIC 0    /* three passes over global memory, libm exp: f32, or ldv % 4 != 0, or unaligned operands */
+#define UIC_XE_LDS 1        /* bf16, row staged in LDS (ldv <= 16384): log-probs wanted, or no gradient, or score_stats */
+#define UIC_XE_REG 2        /* bf16, gradient, ldv <= 10240: the row in registers */
+#define UIC_XE_REG_WIDE 3   /* bf16, gradient, 10240 < ldv <= 53248: the row in the registers of 1024 threads */
+#define UIC_XE_BIG 4        /* bf16, longer rows: two passes with a running (max, sum) */
+int uic_xe_criterion(int32_t dtype, int32_t M, int32_t N, int32_t V1, int32_t ldv, const float* logits, void* dlogits,
+                     const int64_t* target, int32_t ld_target, int32_t target_col0,
+                     const float* mask, int32_t ld_mask, int32_t mask_col0, const float* inv_den,
+                     const float* grad_scale, int32_t ld_scale, int32_t scale_col0,
+                     float* row_loss, float* logprobs, size_t lp_step_stride, size_t lp_row_stride, int32_t* score_stats,
+                     const int32_t* row_map, int32_t row_map_limit, int32_t* kernel_id, void* stream);
+
 /* utilities */
 int uic_cast_from_f32(int32_t dtype, const float* src, void* dst, size_t n, void* stream);
 int uic_cast_to_f32(int32_t dtype, const void* src, float* dst, size_t n, void* stream);

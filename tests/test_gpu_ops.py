@@ -688,3 +688,76 @@ def test_linear_wgrad_tn_matches_matmul(M, N, K, ldy, ldx, accumulate):
         assert lib.uic_linear_wgrad(L.BF16, M, N, K, L.ptr(dYd), ldy, L.ptr(Xd), ldx, L.ptr(dW), N, L.ptr(ws), ws.numel(), TN_256 | TN_SK(7), L.stream()) != 0
     # ineligible shapes are argument errors, not silent fallbacks
     assert lib.uic_linear_wgrad(L.BF16, M, N, K - 8, L.ptr(dYd), ldy, L.ptr(Xd), ldx, L.ptr(dW), N, L.ptr(ws), ws.numel(), 0, L.stream()) != 0
+
+
+@pytest.mark.parametrize("n", [1, 255, 1025, 100003, 3 * 2 ** 20 + 5])
+def test_grad_sqnorm_matches_a_float64_sum_and_repeats_bit_for_bit(n):
+    """uic_grad_sqnorm (the clip's sum of squares: 16-byte loads, four partial sums per lane, a two-stage reduction) on lengths
+    below one workgroup, off the float4 grid and beyond one trip of the whole grid; the second launch must give the same bits
+    (no floating-point atomics)."""
+    L = _lib()
+    lib = L.load()
+    g = torch.randn(n, generator=torch.Generator().manual_seed(n))
+    gd = dev(g)
+    outs = []
+    for _ in range(2):
+        scratch = torch.full((1024,), float("nan"), device="cuda")
+        out = torch.full((1,), float("nan"), device="cuda")
+        L.check(lib.uic_grad_sqnorm(L.ptr(gd), n, L.ptr(scratch), L.ptr(out), L.stream()))
+        outs.append(out.cpu())
+    ref = float((g.double() ** 2).sum())
+    assert abs(float(outs[0]) - ref) < 1e-5 * ref, (float(outs[0]), ref)
+    assert torch.equal(outs[0], outs[1])
+
+
+@pytest.mark.parametrize("max_norm,bites", [(0.25, True), (1e4, False)])
+def test_adam_step_clip_matches_oracle_on_the_clipped_gradient(max_norm, bites):
+    """uic_grad_sqnorm + uic_adam_step_clip against O.adam_step fed with the gradient as torch.nn.utils.clip_grad_norm_ leaves it
+    (g * grad_scale, times max_norm / (norm + 1e-6) if that is below 1), three steps, grad_scale != 1."""
+    L = _lib()
+    lib = L.load()
+    g = torch.Generator().manual_seed(19)
+    n, gs = 100003, 0.5
+    p0, grads = torch.randn(n, generator=g), [torch.randn(n, generator=g) * 0.01 * (k + 1) for k in range(3)]
+    P = {"w": p0.clone()}
+    m, v = {"w": torch.zeros(n)}, {"w": torch.zeros(n)}
+    pd, md, vd = dev(p0).clone(), torch.zeros(n, device="cuda"), torch.zeros(n, device="cuda")
+    scratch, sq = torch.zeros(1024, device="cuda"), torch.zeros(1, device="cuda")
+    for step, gr in enumerate(grads, 1):
+        scaled = gr * gs
+        coef = max_norm / (float(scaled.double().norm()) + 1e-6)
+        assert (coef < 1) == bites
+        O.adam_step(P, {"w": scaled * coef if coef < 1 else scaled}, m, v, step, 5e-4)
+        gd = dev(gr)
+        L.check(lib.uic_grad_sqnorm(L.ptr(gd), n, L.ptr(scratch), L.ptr(sq), L.stream()))
+        L.check(lib.uic_adam_step_clip(L.ptr(pd), L.ptr(gd), L.ptr(md), L.ptr(vd), n, 5e-4, 0.9, 0.999, 1e-8, step, gs, max_norm, L.ptr(sq),
+                                       L.stream()))
+    torch.cuda.synchronize()
+    assert (pd.cpu() - P["w"]).abs().max().item() < 1e-6
+    assert (p0 - P["w"]).abs().max().item() > 1e-4            # (the steps moved the weights)
+
+
+@pytest.mark.parametrize("N,Lc", [(1, 1), (7, 20), (640, 16)])
+def test_reward_criterion_matches_float64(N, Lc):
+    """uic_reward_criterion (RewardCriterion.forward): rows that start with token 0 (only their first position counts), rows that
+    never end, negative rewards; loss and d loss / d logp against the oracle in float64."""
+    L = _lib()
+    lib = L.load()
+    g = torch.Generator().manual_seed(N * 31 + Lc)
+    logp = -torch.rand(N, Lc, generator=g) * 8
+    seq = torch.randint(1, 50, (N, Lc), generator=g)
+    for n in range(N):
+        if n % 3 == 0:
+            seq[n] = 0                                        # starts with the end token
+        elif n % 3 == 1:
+            seq[n, int(torch.randint(0, Lc, (1,), generator=g)):] = 0
+    reward = torch.randn(N, Lc, generator=g)
+    assert N < 3 or (reward < 0).any()
+    lr = logp.double().requires_grad_(True)
+    ref = O.reward_criterion(lr, seq, reward.double())
+    ref.backward()
+    loss, dlogp = torch.full((1,), float("nan"), device="cuda"), torch.full((N, Lc), float("nan"), device="cuda")
+    L.check(lib.uic_reward_criterion(N, Lc, L.ptr(dev(logp)), L.ptr(dev(seq)), L.ptr(dev(reward)), L.ptr(loss), L.ptr(dlogp), L.stream()))
+    torch.cuda.synchronize()
+    assert abs(loss.item() - ref.item()) < 1e-5, (loss.item(), ref.item())
+    assert (dlogp.cpu().double() - lr.grad).abs().max().item() < 1e-5

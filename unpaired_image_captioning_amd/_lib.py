@@ -29,6 +29,9 @@ REC_FWD_CHAIN, REC_BWD_PERSIST, REC_SAFE, REC_STAMPS, REC_EARLY_GRADS, REC_NO_F3
 STEP_MARKS = 11          # UIC_STEP_MARKS
 
 
+XE_GENERIC, XE_LDS, XE_REG, XE_REG_WIDE, XE_BIG = 0, 1, 2, 3, 4     # UIC_XE_*: the kernel uic_xe_criterion launched
+XE_KERNEL_NAMES = ("xe_kernel", "xe_lds_kernel", "xe_reg_kernel", "xe_reg_wide_kernel", "xe_big_kernel")
+
 MAX_LOGIT_LAYERS = 4
 ENSEMBLE_MAX = 8        # UIC_ENSEMBLE_MAX
 SITE_LOGIT_H0 = 8       # + hidden logit block
@@ -330,6 +333,9 @@ _SIGS = {
     "uic_lm_criterion": (C.c_int, [C.c_int32] * 3 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                    C.c_void_p, C.c_void_p, C.c_void_p, C.c_float, C.c_void_p]),
     "uic_reward_criterion": (C.c_int, [C.c_int32, C.c_int32] + [C.c_void_p] * 6),
+    "uic_xe_criterion": (C.c_int, [C.c_int32] * 5 + [C.c_void_p, C.c_void_p] + [C.c_void_p, C.c_int32, C.c_int32] * 2 + [C.c_void_p] +
+                         [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
+                                                               C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
     "uic_cast_from_f32": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uic_cast_to_f32": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uic_transpose": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -332,6 +332,26 @@ int uic_reward_criterion(int32_t N, int32_t L, const float* logp, const int64_t*
   return UIC_OK;
 }
 
+int uic_xe_criterion(int32_t dtype, int32_t M, int32_t N, int32_t V1, int32_t ldv, const float* logits, void* dlogits,
+                     const int64_t* target, int32_t ld_target, int32_t target_col0,
+                     const float* mask, int32_t ld_mask, int32_t mask_col0, const float* inv_den,
+                     const float* grad_scale, int32_t ld_scale, int32_t scale_col0,
+                     float* row_loss, float* logprobs, size_t lp_step_stride, size_t lp_row_stride, int32_t* score_stats,
+                     const int32_t* row_map, int32_t row_map_limit, int32_t* kernel_id, void* stream) {
+  UIC_REQUIRE(dtype == UIC_F32 || dtype == UIC_BF16, "xe_criterion: bad dtype %d", dtype);
+  UIC_REQUIRE(M >= 0 && N > 0 && V1 > 0 && ldv >= V1, "xe_criterion: M=%d N=%d V1=%d ldv=%d", M, N, V1, ldv);
+  UIC_REQUIRE(target || logprobs, "xe_criterion: nothing to compute (no target, no logprobs)");
+  UicXeParams x;
+  memset(&x, 0, sizeof(x));
+  x.dtype = dtype; x.M = M; x.N = N; x.V1 = V1; x.ldv = ldv; x.logits = logits; x.dlogits = dlogits; x.write_grad = dlogits != nullptr;
+  x.target = target; x.ldtarget = ld_target; x.target_col0 = target_col0;
+  x.mask = mask; x.ldmask = ld_mask; x.mask_col0 = mask_col0; x.inv_den = inv_den;
+  x.grad_scale = grad_scale; x.ldscale = ld_scale; x.scale_col0 = scale_col0;
+  x.row_loss = row_loss; x.logprobs = logprobs; x.lp_step_stride = lp_step_stride; x.lp_row_stride = lp_row_stride;
+  x.score_stats = score_stats; x.row_map = row_map; x.row_map_limit = row_map_limit;
+  return uic_xe_launch(x, (hipStream_t)stream, kernel_id);
+}
+
 int uic_cast_from_f32(int32_t dtype, const float* src, void* dst, size_t n, void* stream) {
   return uic_cast_f32_launch(dtype, src, dst, n, (hipStream_t)stream);
 }

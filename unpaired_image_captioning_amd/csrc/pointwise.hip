@@ -2159,7 +2159,7 @@ int uic_scatter_rows_launch(const void* src, const int* map, void* dst, int dst_
   return UIC_OK;
 }
 
-int uic_xe_launch(const UicXeParams& p, hipStream_t s) {
+int uic_xe_launch(const UicXeParams& p, hipStream_t s, int32_t* kernel_id) {
   UIC_REQUIRE(p.logits && p.N > 0, "xe: null logits or N=0");
   UIC_REQUIRE(!p.write_grad || (p.target && ((p.mask && p.inv_den) || p.grad_scale)), "xe: gradient needs target and mask+inv_den or grad_scale");
   UIC_REQUIRE(!p.write_grad || p.dlogits, "xe: null dlogits");
@@ -2172,28 +2172,33 @@ int uic_xe_launch(const UicXeParams& p, hipStream_t s) {
       !p.logprobs && !p.score_stats && ((uintptr_t)p.dlogits & 7) == 0) {
     hipLaunchKernelGGL(xe_reg_kernel<bf16_t>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (bf16_t*)p.dlogits);
     UIC_LAUNCH_CHECK("xe_reg_kernel");
+    if (kernel_id) *kernel_id = UIC_XE_REG;
     return UIC_OK;
   }
   if (p.dtype == UIC_BF16 && p.ldv % 4 == 0 && p.ldv > XE_RCH * NT * 4 && p.ldv <= XE_WCH * XE_WTH * 4 && ((uintptr_t)p.logits & 15) == 0 &&
       p.write_grad && p.target && !p.logprobs && ((uintptr_t)p.dlogits & 7) == 0) {
     hipLaunchKernelGGL(xe_reg_wide_kernel<bf16_t>, dim3(p.M), dim3(XE_WTH), 0, s, p, p.logits, (bf16_t*)p.dlogits);
     UIC_LAUNCH_CHECK("xe_reg_wide_kernel");
+    if (kernel_id) *kernel_id = UIC_XE_REG_WIDE;
     return UIC_OK;
   }
   if (p.dtype == UIC_BF16 && p.ldv % 4 == 0 && row_bytes <= 64 * 1024 && ((uintptr_t)p.logits & 15) == 0) {
     // bf16 path: LDS-staged row + hardware exp (the f32 parity path keeps libm exp)
     hipLaunchKernelGGL(xe_lds_kernel<bf16_t>, dim3(p.M), dim3(NT), row_bytes, s, p, p.logits, (bf16_t*)p.dlogits);
     UIC_LAUNCH_CHECK("xe_lds_kernel");
+    if (kernel_id) *kernel_id = UIC_XE_LDS;
     return UIC_OK;
   }
   if (p.dtype == UIC_BF16 && p.ldv % 4 == 0 && ((uintptr_t)p.logits & 15) == 0 && (!p.dlogits || ((uintptr_t)p.dlogits & 7) == 0)) {
     hipLaunchKernelGGL(xe_big_kernel<bf16_t>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (bf16_t*)p.dlogits);
     UIC_LAUNCH_CHECK("xe_big_kernel");
+    if (kernel_id) *kernel_id = UIC_XE_BIG;
     return UIC_OK;
   }
   DISPATCH_T(p.dtype, hipLaunchKernelGGL(xe_kernel<bf16_t>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (bf16_t*)p.dlogits),
              hipLaunchKernelGGL(xe_kernel<float>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (float*)p.dlogits));
   UIC_LAUNCH_CHECK("xe_kernel");
+  if (kernel_id) *kernel_id = UIC_XE_GENERIC;
   return UIC_OK;
 }
 int uic_logsoftmax_bwd_launch(int dtype, void* dlogits, int M, int V1, int ldv, int N, const float* g,

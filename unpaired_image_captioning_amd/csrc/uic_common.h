@@ -614,7 +614,13 @@ struct UicXeParams {
                                  // [0, row_map_limit) -- the list's -1 padding -- are rows with zero gradient and no loss entry
   int row_map_limit;
 };
-int uic_xe_launch(const UicXeParams& p, hipStream_t s);
+// kernel_id (host, optional): which of the five kernels ran (UIC_XE_GENERIC ... UIC_XE_BIG, include/uic_hip.h)
+#define UIC_XE_GENERIC 0             /* (the same lines as in include/uic_hip.h) */
+#define UIC_XE_LDS 1
+#define UIC_XE_REG 2
+#define UIC_XE_REG_WIDE 3
+#define UIC_XE_BIG 4
+int uic_xe_launch(const UicXeParams& p, hipStream_t s, int32_t* kernel_id = nullptr);
 // rows by index: out[m] = src[map[m]] (rows [M, Mpad) of out, and rows whose index is outside [0, src_rows), cleared) /
 // dst[map[m]] = src[m] (indices outside [0, dst_rows) skipped); row_bytes % 16 == 0
 // the ascending list of the positions t * N + n (p < M) with mask[n * ld + col0 + t] != 0, padded with -1 up to out_len entries
