@@ -750,450 +750,7 @@ __global__ void sample_fixup_kernel(int N, int L, int ld, const int* n_unfinishe
   }
 }
 
-// ------------------------------------------------------------------ log-softmax + LanguageModelCriterion
-__device__ __forceinline__ float block_reduce_max(float v, float* s_buf) {
-  v = uic_wave_max(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s_buf[wave] = v;
-  __syncthreads();
-  float r = s_buf[0];
-  for (int i = 1; i < NT / 64; ++i) r = fmaxf(r, s_buf[i]);
-  return r;
-}
-__device__ __forceinline__ float block_reduce_sum(float v, float* s_buf) {
-  v = uic_wave_sum(v);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) s_buf[wave] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < NT / 64; ++i) r += s_buf[i];
-  return r;
-}
-
-// arg-max of a row (lowest index on ties) for the accuracy counters of NMT_loss.score; `src` may be LDS or global
-__device__ __forceinline__ int block_argmax(const float* src, int V1, int* s_bi, float* s_bv) {
-  float bv = -INFINITY;
-  int bi = 0x7fffffff;
-  for (int v = threadIdx.x; v < V1; v += NT) {
-    const float x = src[v];
-    if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  __syncthreads();
-  if ((threadIdx.x & 63) == 0) { s_bv[threadIdx.x >> 6] = bv; s_bi[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  bv = s_bv[0]; bi = s_bi[0];
-  for (int w2 = 1; w2 < NT / 64; ++w2)
-    if (s_bv[w2] > bv || (s_bv[w2] == bv && s_bi[w2] < bi)) { bv = s_bv[w2]; bi = s_bi[w2]; }
-  return bi;
-}
-
-// One block per (t, n) row of logits: log_softmax (AttModel.py:163) fused with the masked NLL
-// and its gradient (criterion.py:143-150): d logits = (softmax - onehot) * mask / sum(mask).
-template <typename T>
-__global__ __launch_bounds__(NT) void xe_kernel(const UicXeParams p, const float* __restrict__ logits, T* __restrict__ dlogits) {
-  __shared__ float s_buf[NT / 64];
-  const int m = blockIdx.x;
-  const int mr = p.row_map ? p.row_map[m] : m;       // (row_map: the rows are a compacted list of (step, row) positions;
-  const bool pad = p.row_map && (unsigned)mr >= (unsigned)p.row_map_limit;   //  -1 (or out of range) = a padding row: zero gradient, no loss entry)
-  const int mo = pad ? 0 : mr;
-  const int t = mo / p.N, n = mo - t * p.N;
-  const float* row = logits + (size_t)m * p.ldv;
-  float mx = -INFINITY;
-  for (int v = threadIdx.x; v < p.V1; v += NT) mx = fmaxf(mx, row[v]);
-  mx = block_reduce_max(mx, s_buf);
-  float sum = 0.f;
-  for (int v = threadIdx.x; v < p.V1; v += NT) sum += expf(row[v] - mx);
-  sum = block_reduce_sum(sum, s_buf);
-  const float lse = mx + logf(sum);
-  long y = 0;
-  float mk = 0.f;
-  if (p.target) {
-    y = pad ? 0 : p.target[(size_t)n * p.ldtarget + p.target_col0 + t];
-    mk = p.mask && !pad ? p.mask[(size_t)n * p.ldmask + p.mask_col0 + t] : 0.f;
-    if (p.score_stats) {
-      __shared__ float s_bv[NT / 64];
-      __shared__ int s_bi[NT / 64];
-      const int am = block_argmax(row, p.V1, s_bi, s_bv);
-      if (threadIdx.x == 0 && y != 0) {
-        atomicAdd(&p.score_stats[1], 1);
-        if (am == (int)y) atomicAdd(&p.score_stats[0], 1);
-      }
-    }
-    if (y < 0 || y >= p.V1) y = 0;
-    if (threadIdx.x == 0 && !pad) p.row_loss[m] = -(row[y] - lse) * mk;
-  }
-  if (p.logprobs) {
-    float* lp = p.logprobs + (size_t)n * p.lp_row_stride + (size_t)t * p.lp_step_stride;
-    for (int v = threadIdx.x; v < p.V1; v += NT) lp[v] = row[v] - lse;
-  }
-  if (p.write_grad) {
-    const float sc = p.grad_scale ? p.grad_scale[(size_t)n * p.ldscale + p.scale_col0 + t] : mk * p.inv_den[0];
-    T* d = dlogits + (size_t)m * p.ldv;
-    for (int v = threadIdx.x; v < p.ldv; v += NT) {
-      float g = 0.f;
-      if (v < p.V1) g = (expf(row[v] - lse) - (v == y ? 1.f : 0.f)) * sc;
-      d[v] = uic_from_f<T>(g);
-    }
-  }
-}
-
-// Rows too long for LDS (the 50 004-word NMT generator: 200 KB per row): TWO passes over the row instead of three --
-// pass 1 keeps a running (max, sum of exp) per thread (rescaled when the max moves) together with the arg-max, pass 2
-// writes the gradient -- with 16-byte loads.  The arg-max feeds the accuracy counters of NMT_loss.score
-// (criterion.py:175-184), which otherwise cost a third pass of their own.
-template <typename T>
-__global__ __launch_bounds__(NT) void xe_big_kernel(const UicXeParams p, const float* __restrict__ logits, T* __restrict__ dlogits) {
-  __shared__ float s_m[NT / 64], s_s[NT / 64], s_bv[NT / 64];
-  __shared__ int s_bi[NT / 64];
-  const int m = blockIdx.x;
-  const int mr = p.row_map ? p.row_map[m] : m;       // (row_map: the rows are a compacted list of (step, row) positions;
-  const bool pad = p.row_map && (unsigned)mr >= (unsigned)p.row_map_limit;   //  -1 (or out of range) = a padding row: zero gradient, no loss entry)
-  const int mo = pad ? 0 : mr;
-  const int t = mo / p.N, n = mo - t * p.N;
-  const float* row = logits + (size_t)m * p.ldv;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float mx = -INFINITY, sum = 0.f, bv = -INFINITY;
-  int bi = 0x7fffffff;
-  auto take = [&](float x, int v) {
-    if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
-    if (x > mx) { sum = sum * __expf(mx - x) + 1.f; mx = x; }
-    else if (mx != -INFINITY) sum += __expf(x - mx);          // (x = mx = -inf contributes nothing)
-  };
-  for (int v = threadIdx.x * 4; v < p.V1; v += NT * 4) {
-    const float4 x = *(const float4*)(row + v);            // ldv is a multiple of 4 and >= V1: in bounds
-    take(x.x, v);
-    if (v + 1 < p.V1) take(x.y, v + 1);
-    if (v + 2 < p.V1) take(x.z, v + 2);
-    if (v + 3 < p.V1) take(x.w, v + 3);
-  }
-  auto merge = [&](float om, float os, float ov, int oi) {
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    const float nm = fmaxf(mx, om);
-    if (nm != -INFINITY) sum = sum * __expf(mx - nm) + os * __expf(om - nm);
-    mx = nm;
-  };
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1)
-    merge(__shfl_xor(mx, o, 64), __shfl_xor(sum, o, 64), __shfl_xor(bv, o, 64), __shfl_xor(bi, o, 64));
-  if (lane == 0) { s_m[wave] = mx; s_s[wave] = sum; s_bv[wave] = bv; s_bi[wave] = bi; }
-  __syncthreads();
-  mx = s_m[0]; sum = s_s[0]; bv = s_bv[0]; bi = s_bi[0];
-#pragma unroll
-  for (int w2 = 1; w2 < NT / 64; ++w2) merge(s_m[w2], s_s[w2], s_bv[w2], s_bi[w2]);
-  const float lse = mx + logf(sum);
-  long y = 0;
-  float mk = 0.f;
-  if (p.target) {
-    y = pad ? 0 : p.target[(size_t)n * p.ldtarget + p.target_col0 + t];
-    mk = p.mask && !pad ? p.mask[(size_t)n * p.ldmask + p.mask_col0 + t] : 0.f;
-    if (threadIdx.x == 0 && p.score_stats && y != 0) {
-      atomicAdd(&p.score_stats[1], 1);
-      if (bi == (int)y) atomicAdd(&p.score_stats[0], 1);
-    }
-    if (y < 0 || y >= p.V1) y = 0;
-    if (threadIdx.x == 0 && !pad) p.row_loss[m] = -(row[y] - lse) * mk;
-  }
-  if (p.logprobs) {
-    float* lp = p.logprobs + (size_t)n * p.lp_row_stride + (size_t)t * p.lp_step_stride;
-    for (int v = threadIdx.x; v < p.V1; v += NT) lp[v] = row[v] - lse;
-  }
-  if (p.write_grad) {
-    const float sc = p.grad_scale ? p.grad_scale[(size_t)n * p.ldscale + p.scale_col0 + t] : mk * p.inv_den[0];
-    T* d = dlogits + (size_t)m * p.ldv;
-    for (int v = threadIdx.x * 4; v < p.ldv; v += NT * 4) {
-      const float4 x = *(const float4*)(row + v);
-      const float xs[4] = {x.x, x.y, x.z, x.w};
-      float g[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int vv = v + j;
-        g[j] = vv < p.V1 ? (__expf(xs[j] - lse) - (vv == y ? 1.f : 0.f)) * sc : 0.f;
-      }
-      if constexpr (sizeof(T) == 2) {
-        *(uint2*)(d + v) = make_uint2(uic_pack_bf16x2(g[0], g[1]), uic_pack_bf16x2(g[2], g[3]));
-      } else {
-        *(float4*)(d + v) = make_float4(g[0], g[1], g[2], g[3]);
-      }
-    }
-  }
-}
-
-// Same, with the logits row staged once in LDS (rows up to 64 KB): one HBM read of the 413 MB logits
-// tensor instead of three.
-template <typename T>
-__global__ __launch_bounds__(NT) void xe_lds_kernel(const UicXeParams p, const float* __restrict__ logits, T* __restrict__ dlogits) {
-  extern __shared__ __attribute__((aligned(16))) float s_row[];
-  __shared__ float s_buf[NT / 64];
-  const int m = blockIdx.x;
-  const int mr = p.row_map ? p.row_map[m] : m;       // (row_map: the rows are a compacted list of (step, row) positions;
-  const bool pad = p.row_map && (unsigned)mr >= (unsigned)p.row_map_limit;   //  -1 (or out of range) = a padding row: zero gradient, no loss entry)
-  const int mo = pad ? 0 : mr;
-  const int t = mo / p.N, n = mo - t * p.N;
-  const float* row = logits + (size_t)m * p.ldv;
-  float mx = -INFINITY;
-  for (int v = threadIdx.x * 4; v < p.ldv; v += NT * 4) {
-    const float4 x = *(const float4*)(row + v);
-    *(float4*)(s_row + v) = x;
-    if (v < p.V1) mx = fmaxf(mx, x.x);
-    if (v + 1 < p.V1) mx = fmaxf(mx, x.y);
-    if (v + 2 < p.V1) mx = fmaxf(mx, x.z);
-    if (v + 3 < p.V1) mx = fmaxf(mx, x.w);
-  }
-  mx = block_reduce_max(mx, s_buf);
-  float sum = 0.f;
-  for (int v = threadIdx.x; v < p.V1; v += NT) sum += __expf(s_row[v] - mx);
-  sum = block_reduce_sum(sum, s_buf);
-  const float lse = mx + logf(sum);
-  long y = 0;
-  float mk = 0.f;
-  if (p.target) {
-    y = pad ? 0 : p.target[(size_t)n * p.ldtarget + p.target_col0 + t];
-    mk = p.mask && !pad ? p.mask[(size_t)n * p.ldmask + p.mask_col0 + t] : 0.f;
-    if (p.score_stats) {
-      __shared__ float s_bv[NT / 64];
-      __shared__ int s_bi[NT / 64];
-      const int am = block_argmax(s_row, p.V1, s_bi, s_bv);
-      if (threadIdx.x == 0 && y != 0) {
-        atomicAdd(&p.score_stats[1], 1);
-        if (am == (int)y) atomicAdd(&p.score_stats[0], 1);
-      }
-    }
-    if (y < 0 || y >= p.V1) y = 0;
-    if (threadIdx.x == 0 && !pad) p.row_loss[m] = -(s_row[y] - lse) * mk;
-  }
-  if (p.logprobs) {
-    float* lp = p.logprobs + (size_t)n * p.lp_row_stride + (size_t)t * p.lp_step_stride;
-    for (int v = threadIdx.x; v < p.V1; v += NT) lp[v] = s_row[v] - lse;
-  }
-  if (p.write_grad) {
-    const float sc = p.grad_scale ? p.grad_scale[(size_t)n * p.ldscale + p.scale_col0 + t] : mk * p.inv_den[0];
-    T* d = dlogits + (size_t)m * p.ldv;
-    for (int v = threadIdx.x * 4; v < p.ldv; v += NT * 4) {
-      float g[4];
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int vv = v + j;
-        g[j] = vv < p.V1 ? (__expf(s_row[vv] - lse) - (vv == y ? 1.f : 0.f)) * sc : 0.f;
-      }
-      if constexpr (sizeof(T) == 2) {
-        *(uint2*)(d + v) = make_uint2(uic_pack_bf16x2(g[0], g[1]), uic_pack_bf16x2(g[2], g[3]));
-      } else {
-        *(float4*)(d + v) = make_float4(g[0], g[1], g[2], g[3]);
-      }
-    }
-  }
-}
-
-// Training-path variant (loss + d logits, no log-prob output): the row lives in REGISTERS (up to XE_RCH float4 per thread), one
-// HBM read, one exp per element (the e^{x - max} of the normaliser pass is reused for the gradient), no LDS staging -- 8 instead
-// of 4 workgroups per CU keep more loads in flight on the HBM-bound pass over the logits.
-constexpr int XE_RCH = 10;     // rows up to 10 * NT * 4 = 10 240 columns
-template <typename T>
-__global__ __launch_bounds__(NT) void xe_reg_kernel(const UicXeParams p, const float* __restrict__ logits, T* __restrict__ dlogits) {
-  __shared__ float s_buf[NT / 64];
-  __shared__ float s_y;
-  const int m = blockIdx.x;
-  const int mr = p.row_map ? p.row_map[m] : m;       // (row_map: the rows are a compacted list of (step, row) positions;
-  const bool pad = p.row_map && (unsigned)mr >= (unsigned)p.row_map_limit;   //  -1 (or out of range) = a padding row: zero gradient, no loss entry)
-  const int mo = pad ? 0 : mr;
-  const int t = mo / p.N, n = mo - t * p.N;
-  const float* row = logits + (size_t)m * p.ldv;
-  long y = pad ? 0 : p.target[(size_t)n * p.ldtarget + p.target_col0 + t];
-  const float mk = p.mask && !pad ? p.mask[(size_t)n * p.ldmask + p.mask_col0 + t] : 0.f;
-  if (y < 0 || y >= p.V1) y = 0;
-  if (mk == 0.f && !p.grad_scale) {
-    // a position behind its caption's end (a quarter of the benchmark's, a third of COCO's): loss 0 x (.), d logits = 0 x softmax - 0 --
-    // exact zeros whatever the logits are, so the row is not read (round 6; uniform over the workgroup)
-    if (threadIdx.x == 0 && !pad) p.row_loss[m] = 0.f;
-    T* d = dlogits + (size_t)m * p.ldv;
-    for (int v = threadIdx.x * 4; v < p.ldv; v += NT * 4) {
-      if constexpr (sizeof(T) == 2) *(uint2*)(d + v) = make_uint2(0u, 0u);
-      else *(float4*)(d + v) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    return;
-  }
-  float4 x[XE_RCH];
-  float mx = -INFINITY;
-  // Every chunk of the row requested before the first is used, from a clamped address (round 6): behind `if (v < p.ldv)` hipcc
-  // waited for each load at its branch's join -- a thread's ten loads were ten HBM round trips in a row.
-#pragma unroll
-  for (int i = 0; i < XE_RCH; ++i) {
-    const int v = (threadIdx.x + i * NT) * 4;
-    x[i] = *(const float4*)(row + (v < p.ldv ? v : p.ldv - 4));
-  }
-#pragma unroll
-  for (int i = 0; i < XE_RCH; ++i) {
-    const int v = (threadIdx.x + i * NT) * 4;
-    const float4 r = x[i];
-    const bool in = v < p.ldv;
-    x[i].x = in && v < p.V1 ? r.x : -INFINITY; x[i].y = in && v + 1 < p.V1 ? r.y : -INFINITY;
-    x[i].z = in && v + 2 < p.V1 ? r.z : -INFINITY; x[i].w = in && v + 3 < p.V1 ? r.w : -INFINITY;
-    if (in && (long)v <= y && y < (long)v + 4) s_y = y == v ? r.x : y == v + 1 ? r.y : y == v + 2 ? r.z : r.w;
-    mx = fmaxf(mx, fmaxf(fmaxf(x[i].x, x[i].y), fmaxf(x[i].z, x[i].w)));
-  }
-  mx = block_reduce_max(mx, s_buf);
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < XE_RCH; ++i) {        // padded / out-of-row entries hold -inf -> e = 0
-    x[i].x = __expf(x[i].x - mx); x[i].y = __expf(x[i].y - mx); x[i].z = __expf(x[i].z - mx); x[i].w = __expf(x[i].w - mx);
-    sum += (x[i].x + x[i].y) + (x[i].z + x[i].w);
-  }
-  sum = block_reduce_sum(sum, s_buf);       // (its barriers also publish s_y)
-  const float lse = mx + logf(sum);
-  if (threadIdx.x == 0 && !pad) p.row_loss[m] = -(s_y - lse) * mk;
-  const float sc = p.grad_scale ? p.grad_scale[(size_t)n * p.ldscale + p.scale_col0 + t] : mk * p.inv_den[0];
-  const float k = sc / sum;
-  T* d = dlogits + (size_t)m * p.ldv;
-#pragma unroll
-  for (int i = 0; i < XE_RCH; ++i) {
-    const int v = (threadIdx.x + i * NT) * 4;
-    if (v >= p.ldv) continue;
-    float g[4] = {x[i].x * k, x[i].y * k, x[i].z * k, x[i].w * k};
-    const long j = y - (long)v;           // (a dynamic index into g[] would put it in scratch)
-    g[0] -= j == 0 ? sc : 0.f; g[1] -= j == 1 ? sc : 0.f; g[2] -= j == 2 ? sc : 0.f; g[3] -= j == 3 ? sc : 0.f;
-    if constexpr (sizeof(T) == 2) {
-      *(uint2*)(d + v) = make_uint2(uic_pack_bf16x2(g[0], g[1]), uic_pack_bf16x2(g[2], g[3]));
-    } else {
-      *(float4*)(d + v) = make_float4(g[0], g[1], g[2], g[3]);
-    }
-  }
-}
-
-// The same for rows too long for 256 threads' registers -- the pivot NMT's generator, 50 004 words = 200 KB per row: a workgroup
-// of 1024 threads holds the row (13 float4 per thread), so the criterion reads the 397 MB of logits ONCE (xe_big_kernel: twice)
-// and keeps the arg-max for the accuracy counters of NMT_loss.score (criterion.py:175-184) on the way.
-constexpr int XE_WTH = 1024, XE_WCH = 13;     // rows up to 13 * 1024 * 4 = 53 248 columns (512 threads x 26 float4 at two
-                                              // workgroups per CU: 128 registers per lane, 307 spilled -- 427 us)
-template <typename T>
-__global__ __launch_bounds__(XE_WTH) void xe_reg_wide_kernel(const UicXeParams p, const float* __restrict__ logits, T* __restrict__ dlogits) {
-  __shared__ float s_f[XE_WTH / 64], s_bv[XE_WTH / 64];
-  __shared__ int s_bi[XE_WTH / 64];
-  __shared__ float s_y;
-  const int m = blockIdx.x;
-  const int mr = p.row_map ? p.row_map[m] : m;       // (row_map: the rows are a compacted list of (step, row) positions;
-  const bool pad = p.row_map && (unsigned)mr >= (unsigned)p.row_map_limit;   //  -1 (or out of range) = a padding row: zero gradient, no loss entry)
-  const int mo = pad ? 0 : mr;
-  const int t = mo / p.N, n = mo - t * p.N;
-  const float* row = logits + (size_t)m * p.ldv;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const long y0 = pad ? 0 : p.target[(size_t)n * p.ldtarget + p.target_col0 + t];
-  const float mk = p.mask && !pad ? p.mask[(size_t)n * p.ldmask + p.mask_col0 + t] : 0.f;
-  const long y = y0 < 0 || y0 >= p.V1 ? 0 : y0;
-  if (mk == 0.f && !p.grad_scale && !(p.score_stats && y0 != 0)) {      // (a padded target position: see xe_reg_kernel)
-    if (threadIdx.x == 0 && !pad) p.row_loss[m] = 0.f;
-    T* d = dlogits + (size_t)m * p.ldv;
-    for (int v = threadIdx.x * 4; v < p.ldv; v += XE_WTH * 4) {
-      if constexpr (sizeof(T) == 2) *(uint2*)(d + v) = make_uint2(0u, 0u);
-      else *(float4*)(d + v) = make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-    return;
-  }
-  float4 x[XE_WCH];
-  float mx = -INFINITY, bv = -INFINITY;
-  int bi = 0x7fffffff;
-  // (all thirteen chunks requested before the first is used, from clamped addresses: see xe_reg_kernel)
-#pragma unroll
-  for (int i = 0; i < XE_WCH; ++i) {
-    const int v = (threadIdx.x + i * XE_WTH) * 4;
-    x[i] = *(const float4*)(row + (v < p.ldv ? v : p.ldv - 4));
-  }
-#pragma unroll
-  for (int i = 0; i < XE_WCH; ++i) {
-    const int v = (threadIdx.x + i * XE_WTH) * 4;
-    {
-      const float4 r = x[i];
-      const bool in = v < p.ldv;
-      x[i].x = in && v < p.V1 ? r.x : -INFINITY; x[i].y = in && v + 1 < p.V1 ? r.y : -INFINITY;
-      x[i].z = in && v + 2 < p.V1 ? r.z : -INFINITY; x[i].w = in && v + 3 < p.V1 ? r.w : -INFINITY;
-      if (in && (long)v <= y && y < (long)v + 4) s_y = y == v ? r.x : y == v + 1 ? r.y : y == v + 2 ? r.z : r.w;
-    }
-    // (ascending index inside the thread: a later equal value does not replace the arg-max)
-    if (x[i].x > bv) { bv = x[i].x; bi = v; }
-    if (x[i].y > bv) { bv = x[i].y; bi = v + 1; }
-    if (x[i].z > bv) { bv = x[i].z; bi = v + 2; }
-    if (x[i].w > bv) { bv = x[i].w; bi = v + 3; }
-  }
-  mx = bv;
-  // workgroup maximum and its lowest index
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ov = __shfl_xor(bv, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-  }
-  if (lane == 0) { s_bv[wave] = bv; s_bi[wave] = bi; }
-  __syncthreads();
-  bv = s_bv[0]; bi = s_bi[0];
-#pragma unroll
-  for (int w2 = 1; w2 < XE_WTH / 64; ++w2)
-    if (s_bv[w2] > bv || (s_bv[w2] == bv && s_bi[w2] < bi)) { bv = s_bv[w2]; bi = s_bi[w2]; }
-  mx = bv;
-  float sum = 0.f;
-#pragma unroll
-  for (int i = 0; i < XE_WCH; ++i) {        // padded / out-of-row entries hold -inf -> e = 0
-    x[i].x = __expf(x[i].x - mx); x[i].y = __expf(x[i].y - mx); x[i].z = __expf(x[i].z - mx); x[i].w = __expf(x[i].w - mx);
-    sum += (x[i].x + x[i].y) + (x[i].z + x[i].w);
-  }
-  sum = uic_wave_sum(sum);
-  if (lane == 0) s_f[wave] = sum;
-  __syncthreads();                          // (also publishes s_y)
-  sum = 0.f;
-#pragma unroll
-  for (int w2 = 0; w2 < XE_WTH / 64; ++w2) sum += s_f[w2];
-  const float lse = mx + logf(sum);
-  if (threadIdx.x == 0) {
-    p.row_loss[m] = -(s_y - lse) * mk;
-    if (p.score_stats && y0 != 0) {
-      atomicAdd(&p.score_stats[1], 1);
-      if (bi == (int)y0) atomicAdd(&p.score_stats[0], 1);
-    }
-  }
-  const float sc = p.grad_scale ? p.grad_scale[(size_t)n * p.ldscale + p.scale_col0 + t] : mk * p.inv_den[0];
-  const float k = sc / sum;
-  T* d = dlogits + (size_t)m * p.ldv;
-#pragma unroll
-  for (int i = 0; i < XE_WCH; ++i) {
-    const int v = (threadIdx.x + i * XE_WTH) * 4;
-    if (v >= p.ldv) continue;
-    float g[4] = {x[i].x * k, x[i].y * k, x[i].z * k, x[i].w * k};
-    const long j = y - (long)v;
-    g[0] -= j == 0 ? sc : 0.f; g[1] -= j == 1 ? sc : 0.f; g[2] -= j == 2 ? sc : 0.f; g[3] -= j == 3 ? sc : 0.f;
-    if constexpr (sizeof(T) == 2) {
-      *(uint2*)(d + v) = make_uint2(uic_pack_bf16x2(g[0], g[1]), uic_pack_bf16x2(g[2], g[3]));
-    } else {
-      *(float4*)(d + v) = make_float4(g[0], g[1], g[2], g[3]);
-    }
-  }
-}
-
-// API-compat backward: upstream grad g wrt log-probs [n][t][v]; d logits = g - softmax * sum_v g
-template <typename T>
-__global__ __launch_bounds__(NT) void logsoftmax_bwd_kernel(T* __restrict__ dlogits, int V1, int ldv, int N, const float* __restrict__ g,
-                                                            size_t g_step, size_t g_row, const float* __restrict__ logprobs) {
-  __shared__ float s_buf[NT / 64];
-  const int m = blockIdx.x;
-  const int t = m / N, n = m - t * N;
-  const float* gr = g + (size_t)n * g_row + (size_t)t * g_step;
-  const float* lp = logprobs + (size_t)n * g_row + (size_t)t * g_step;
-  float sum = 0.f;
-  for (int v = threadIdx.x; v < V1; v += NT) sum += gr[v];
-  sum = block_reduce_sum(sum, s_buf);
-  T* d = dlogits + (size_t)m * ldv;
-  for (int v = threadIdx.x; v < ldv; v += NT) {
-    float x = 0.f;
-    if (v < V1) x = gr[v] - expf(lp[v]) * sum;
-    d[v] = uic_from_f<T>(x);
-  }
-}
-
+// ------------------------------------------------------------------ sums (the criterion kernels: criterion.hip)
 constexpr int MS_NT = 1024, MS_U = 16;
 __global__ __launch_bounds__(MS_NT) void masked_sum_kernel(const float* __restrict__ mask, int ldmask, int col0, int N, int TS,
                                                            float* out_sum, float* out_inv) {
@@ -1237,7 +794,7 @@ __global__ __launch_bounds__(NT) void reduce_sum_kernel(const float* __restrict_
 #pragma unroll
     for (int u = 0; u < 8; ++u) s += v[u];
   }
-  s = block_reduce_sum(s, s_buf);
+  s = uic_block_sum<NT>(s, s_buf);
   if (threadIdx.x == 0) out[0] = scale ? s * scale[0] : s;
 }
 
@@ -1287,7 +844,7 @@ __global__ __launch_bounds__(NT) void sqnorm_part_kernel(const float* __restrict
     s0 += (a[0] * a[0] + a[1] * a[1]) + (a[2] * a[2] + a[3] * a[3]);
   }
   for (size_t j = n4 * 4 + (size_t)blockIdx.x * NT + threadIdx.x; j < n; j += stride) s1 += g[j] * g[j];
-  float s = block_reduce_sum((s0 + s1) + (s2 + s3), s_buf);
+  float s = uic_block_sum<NT>((s0 + s1) + (s2 + s3), s_buf);
   if (threadIdx.x == 0) part[blockIdx.x] = s;
 }
 // ONE definition of the element update for both Adam kernels, with floating-point contraction off: the whole-arena kernel and the
@@ -1368,7 +925,7 @@ __global__ __launch_bounds__(NT) void ss_sample_kernel(const float* __restrict__
   const float* row = logits + (size_t)n * ldv;
   float mx = -INFINITY;
   for (int v = threadIdx.x; v < V1; v += NT) mx = fmaxf(mx, row[v]);
-  mx = block_reduce_max(mx, s_buf);
+  mx = uic_block_max<NT>(mx, s_buf);
   const int per = (V1 + NT - 1) / NT;
   const int v_lo = threadIdx.x * per, v_hi = min(V1, v_lo + per);
   float part = 0.f;
@@ -1440,10 +997,10 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const UicSampleParams p
 
   float mx = -INFINITY;
   for (int v = threadIdx.x; v < p.V1; v += NT) mx = fmaxf(mx, row[v]);
-  mx = block_reduce_max(mx, s_buf);
+  mx = uic_block_max<NT>(mx, s_buf);
   float sum = 0.f;
   for (int v = threadIdx.x; v < p.V1; v += NT) sum += ex(row[v] - mx);
-  sum = block_reduce_sum(sum, s_buf);
+  sum = uic_block_sum<NT>(sum, s_buf);
   const float lse = mx + logf(sum);
   if (p.logprobs_out)
     for (int v = threadIdx.x; v < p.V1; v += NT) p.logprobs_out[(size_t)n * p.V1 + v] = row[v] - lse;
@@ -1456,20 +1013,7 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const UicSampleParams p
       const float x = (v == banned) ? -INFINITY : row[v];
       if (x > bv || (x == bv && v < bi)) { bv = x; bi = v; }
     }
-    // wave-level arg-max by shuffles, then one LDS exchange between the four waves (value descending, lowest index on ties)
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
-    }
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) { s_val[threadIdx.x >> 6] = bv; s_idx[threadIdx.x >> 6] = bi; }
-    __syncthreads();
-    bv = s_val[0]; bi = s_idx[0];
-#pragma unroll
-    for (int w2 = 1; w2 < NT / 64; ++w2)
-      if (s_val[w2] > bv || (s_val[w2] == bv && s_idx[w2] < bi)) { bv = s_val[w2]; bi = s_idx[w2]; }
+    uic_block_argmax<NT>(bv, bi, s_val, s_idx);      // (value descending, lowest index on ties)
     choice = bi;
   } else if (p.forced) {
     choice = (int)p.forced[(size_t)n * p.L + t];
@@ -1491,7 +1035,7 @@ __global__ __launch_bounds__(NT) void sample_step_kernel(const UicSampleParams p
       const float up = __shfl_up(incl, o, 64);
       if (lane >= o) incl += up;
     }
-    __syncthreads();                                   // s_buf was last read by block_reduce_sum
+    __syncthreads();                                   // s_buf was last read by uic_block_sum
     if (lane == 63) s_buf[wv] = incl;
     __syncthreads();
     float woff = 0.f, tot = 0.f;
@@ -2159,58 +1703,6 @@ int uic_scatter_rows_launch(const void* src, const int* map, void* dst, int dst_
   return UIC_OK;
 }
 
-int uic_xe_launch(const UicXeParams& p, hipStream_t s, int32_t* kernel_id) {
-  UIC_REQUIRE(p.logits && p.N > 0, "xe: null logits or N=0");
-  UIC_REQUIRE(!p.write_grad || (p.target && ((p.mask && p.inv_den) || p.grad_scale)), "xe: gradient needs target and mask+inv_den or grad_scale");
-  UIC_REQUIRE(!p.write_grad || p.dlogits, "xe: null dlogits");
-  UIC_REQUIRE(!p.target || p.row_loss, "xe: null row_loss");
-  UIC_REQUIRE(!p.row_map || (p.write_grad && p.mask && !p.grad_scale && !p.logprobs),
-              "xe: a row list goes with the masked criterion only (target, mask, gradient; no per-position scale or log-probabilities)");
-  if (p.M == 0) return UIC_OK;
-  const size_t row_bytes = (size_t)p.ldv * 4;
-  if (p.dtype == UIC_BF16 && p.ldv % 4 == 0 && p.ldv <= XE_RCH * NT * 4 && ((uintptr_t)p.logits & 15) == 0 && p.write_grad && p.target &&
-      !p.logprobs && !p.score_stats && ((uintptr_t)p.dlogits & 7) == 0) {
-    hipLaunchKernelGGL(xe_reg_kernel<bf16_t>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (bf16_t*)p.dlogits);
-    UIC_LAUNCH_CHECK("xe_reg_kernel");
-    if (kernel_id) *kernel_id = UIC_XE_REG;
-    return UIC_OK;
-  }
-  if (p.dtype == UIC_BF16 && p.ldv % 4 == 0 && p.ldv > XE_RCH * NT * 4 && p.ldv <= XE_WCH * XE_WTH * 4 && ((uintptr_t)p.logits & 15) == 0 &&
-      p.write_grad && p.target && !p.logprobs && ((uintptr_t)p.dlogits & 7) == 0) {
-    hipLaunchKernelGGL(xe_reg_wide_kernel<bf16_t>, dim3(p.M), dim3(XE_WTH), 0, s, p, p.logits, (bf16_t*)p.dlogits);
-    UIC_LAUNCH_CHECK("xe_reg_wide_kernel");
-    if (kernel_id) *kernel_id = UIC_XE_REG_WIDE;
-    return UIC_OK;
-  }
-  if (p.dtype == UIC_BF16 && p.ldv % 4 == 0 && row_bytes <= 64 * 1024 && ((uintptr_t)p.logits & 15) == 0) {
-    // bf16 path: LDS-staged row + hardware exp (the f32 parity path keeps libm exp)
-    hipLaunchKernelGGL(xe_lds_kernel<bf16_t>, dim3(p.M), dim3(NT), row_bytes, s, p, p.logits, (bf16_t*)p.dlogits);
-    UIC_LAUNCH_CHECK("xe_lds_kernel");
-    if (kernel_id) *kernel_id = UIC_XE_LDS;
-    return UIC_OK;
-  }
-  if (p.dtype == UIC_BF16 && p.ldv % 4 == 0 && ((uintptr_t)p.logits & 15) == 0 && (!p.dlogits || ((uintptr_t)p.dlogits & 7) == 0)) {
-    hipLaunchKernelGGL(xe_big_kernel<bf16_t>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (bf16_t*)p.dlogits);
-    UIC_LAUNCH_CHECK("xe_big_kernel");
-    if (kernel_id) *kernel_id = UIC_XE_BIG;
-    return UIC_OK;
-  }
-  DISPATCH_T(p.dtype, hipLaunchKernelGGL(xe_kernel<bf16_t>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (bf16_t*)p.dlogits),
-             hipLaunchKernelGGL(xe_kernel<float>, dim3(p.M), dim3(NT), 0, s, p, p.logits, (float*)p.dlogits));
-  UIC_LAUNCH_CHECK("xe_kernel");
-  if (kernel_id) *kernel_id = UIC_XE_GENERIC;
-  return UIC_OK;
-}
-int uic_logsoftmax_bwd_launch(int dtype, void* dlogits, int M, int V1, int ldv, int N, const float* g,
-                              size_t g_step_stride, size_t g_row_stride, const float* logprobs, hipStream_t s) {
-  UIC_REQUIRE(dlogits && g && logprobs && N > 0, "logsoftmax_bwd: null pointer");
-  if (M == 0) return UIC_OK;
-  DISPATCH_T(dtype,
-             hipLaunchKernelGGL(logsoftmax_bwd_kernel<bf16_t>, dim3(M), dim3(NT), 0, s, (bf16_t*)dlogits, V1, ldv, N, g, g_step_stride, g_row_stride, logprobs),
-             hipLaunchKernelGGL(logsoftmax_bwd_kernel<float>, dim3(M), dim3(NT), 0, s, (float*)dlogits, V1, ldv, N, g, g_step_stride, g_row_stride, logprobs));
-  UIC_LAUNCH_CHECK("logsoftmax_bwd");
-  return UIC_OK;
-}
 int uic_masked_sum_launch(const float* x, const float* mask, int ldmask, int col0, int N, int T, float* out_sum,
                           float* out_inv, hipStream_t s) {
   (void)x;

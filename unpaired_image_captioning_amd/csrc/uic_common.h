@@ -139,6 +139,53 @@ __device__ __forceinline__ float uic_wave_max(float v) {
   for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
   return v;
 }
+
+// Reductions over a workgroup of NT threads; every thread gets the result.  Wave shuffles first, lane 0 of each wave writes its
+// wave's result to LDS (NT / 64 slots) between two barriers, then every thread folds the slots serially in the order of the
+// waves 0, 1, 2, ... -- one fixed order of operations, so the result does not depend on the schedule.  The leading barrier lets
+// back-to-back calls share one buffer, and callers rely on the pair to publish their own earlier LDS writes.
+template <int NT>
+__device__ __forceinline__ float uic_block_max(float v, float* s_buf) {
+  v = uic_wave_max(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) s_buf[wave] = v;
+  __syncthreads();
+  float r = s_buf[0];
+#pragma unroll
+  for (int i = 1; i < NT / 64; ++i) r = fmaxf(r, s_buf[i]);
+  return r;
+}
+template <int NT>
+__device__ __forceinline__ float uic_block_sum(float v, float* s_buf) {
+  v = uic_wave_sum(v);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  __syncthreads();
+  if (lane == 0) s_buf[wave] = v;
+  __syncthreads();
+  float r = 0.f;
+#pragma unroll
+  for (int i = 0; i < NT / 64; ++i) r += s_buf[i];
+  return r;
+}
+// arg-max: each thread brings its candidate (value bv at index bi; -inf at 0x7fffffff for none) and leaves with the workgroup's.
+// The larger value wins, the LOWEST index among equal values.
+template <int NT>
+__device__ __forceinline__ void uic_block_argmax(float& bv, int& bi, float* s_bv, int* s_bi) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float ov = __shfl_xor(bv, o, 64);
+    const int oi = __shfl_xor(bi, o, 64);
+    if (ov > bv || (ov == bv && oi < bi)) { bv = ov; bi = oi; }
+  }
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) { s_bv[threadIdx.x >> 6] = bv; s_bi[threadIdx.x >> 6] = bi; }
+  __syncthreads();
+  bv = s_bv[0]; bi = s_bi[0];
+#pragma unroll
+  for (int w = 1; w < NT / 64; ++w)
+    if (s_bv[w] > bv || (s_bv[w] == bv && s_bi[w] < bi)) { bv = s_bv[w]; bi = s_bi[w]; }
+}
 #endif  // __HIPCC__
 
 // ---------------------------------------------------------------- GEMM (gemm.hip)
@@ -596,6 +643,7 @@ int uic_h2att_cell_bwd_launch(const UicH2attCellParams& p, hipStream_t s);
 int uic_maxout_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s);   // gates/dgates are [M,5H]; dh = (dh0 + dh1) * dropout
 int uic_sample_fixup_launch(int N, int L, int ld, const int* n_unfinished, int64_t* seq, float* seq_logp, hipStream_t s);
 
+// log-softmax + criterion (criterion.hip)
 struct UicXeParams {
   int dtype, M, V1, ldv;         // logits f32 [M, ldv] in; dlogits [M, ldv] operand dtype out
   const float* logits;
@@ -615,11 +663,6 @@ struct UicXeParams {
   int row_map_limit;
 };
 // kernel_id (host, optional): which of the five kernels ran (UIC_XE_GENERIC ... UIC_XE_BIG, include/uic_hip.h)
-#define UIC_XE_GENERIC 0             /* (the same lines as in include/uic_hip.h) */
-#define UIC_XE_LDS 1
-#define UIC_XE_REG 2
-#define UIC_XE_REG_WIDE 3
-#define UIC_XE_BIG 4
 int uic_xe_launch(const UicXeParams& p, hipStream_t s, int32_t* kernel_id = nullptr);
 // rows by index: out[m] = src[map[m]] (rows [M, Mpad) of out, and rows whose index is outside [0, src_rows), cleared) /
 // dst[map[m]] = src[m] (indices outside [0, dst_rows) skipped); row_bytes % 16 == 0
