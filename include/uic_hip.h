@@ -683,6 +683,54 @@ int uic_xe_criterion(int32_t dtype, int32_t M, int32_t N, int32_t V1, int32_t ld
                      float* row_loss, float* logprobs, size_t lp_step_stride, size_t lp_row_stride, int32_t* score_stats,
                      const int32_t* row_map, int32_t row_map_limit, int32_t* kernel_id, void* stream);
 
+/* nn.BatchNorm1d inside att_embed (P/models/AttModel.py:78-84, --use_bn 1|2; P/opts.py:52 makes 1 the default), applied by
+ * pack_wrapper (:44-53) to the packed live regions only -- the batch-norm launches of the model steps on their own
+ * (csrc/batchnorm.hip).  All arithmetic is f32 whatever the operand dtype.
+ *   x / y / out  [NR, C] row-major in their dtype (UIC_DTYPE_F32 / UIC_DTYPE_BF16), 16-byte aligned (f32) / 8-byte aligned (bf16);
+ *           NR > 0, C a positive multiple of 4.  Outputs must not overlap inputs (d of uic_batchnorm_backward is in place).
+ *   row_len (optional, device int32[ceil(NR / R)], R > 0): row n * R + r is LIVE iff row_len == NULL or r < row_len[n].  Dead rows
+ *           are never READ by the statistics or the backward pass, whatever they hold (NaN and inf included).  R is ignored when
+ *           row_len == NULL.
+ *   stat    f32 [2C] = {batch mean, 1 / sqrt(biased variance + eps)} over the live rows.
+ *   part    scratch of uic_batchnorm_scratch_floats(NR, C) floats (0 = bad arguments);  red  f32 [3C] = {n, dbeta, dgamma}.
+ * uic_batchnorm_stats: stat from x.  Per column, shifted sums (v - K, K = the first live row of a chunk of rows) per chunk, the
+ *   chunks merged with Chan's formula: a column of large mean and small spread keeps its variance, a constant column has variance
+ *   exactly 0 and mean exactly its value.  With no live row at all stat = {0, 1 / sqrt(eps)}.  run_mean / run_var (optional, f32
+ *   [C]) are updated as nn.BatchNorm1d does in training: run <- (1 - momentum) run + momentum {mean, UNBIASED variance}.  `rep`
+ *   >= 1: every row stands for `rep` identical rows (features given once per image, seq_per_img caption rows each) -- mean and
+ *   biased variance are unchanged, the unbiased variance is rep M2 / (rep n - 1), M2 = sum (x - mean)^2 over the n live rows.
+ *   When n rep <= 1 (one live row or none, where nn.BatchNorm1d refuses the batch) run_var takes the BIASED variance, that is 0.
+ * uic_batchnorm_stats_running: stat = {run_mean, 1 / sqrt(run_var + eps)} (eval mode).
+ * uic_batchnorm_apply: out = gamma (x - mean) rstd + beta on live rows (gamma / beta optional f32 [C]: 1 / 0).  zero_padded = 1
+ *   writes dead rows as zeros without reading them; with zero_padded = 0 row_len is ignored and the output of dead rows is
+ *   unspecified (they are normalised like any row).
+ * uic_batchnorm_backward: d (f32 [NR, C], IN PLACE) holds d loss / d out on entry and d loss / d y on return, y the layer's input
+ *   in `dtype`: d <- gamma rstd (d - [training] (dbeta + yhat dgamma) / n), yhat = (y - mean) rstd, n = live rows; dead rows of d
+ *   are written as zeros.  gamma is required.  dgamma = sum d yhat, dbeta = sum d over the live rows (f32 [C], optional: red
+ *   always receives them).  training = 0: the eval-mode gradient (statistics are constants).  With no live row d is all zeros.
+ * uic_batchnorm_fold_weight / _fold_grad: BatchNorm1d in FRONT of a Linear(D, H), its affine part folded into the Linear so that
+ *   the GEMM reads xhat and backward needs no extra GEMM.  D > 0 and H > 0, D need not be a multiple of 4.
+ *     fold_weight:  Weff[h, c] = W[h, c] gamma[c] (in `dtype`),  beff[h] = b[h] + sum_c W[h, c] beta[c]   (W f32 [H, D])
+ *     fold_grad:    in dW = dW' = d_pre^T xhat [H, D] and db = colsum(d_pre) [H] (gradients w.r.t. Weff and beff);
+ *                   out dgamma[c] = sum_h W[h, c] dW'[h, c],  dbeta[c] = sum_h W[h, c] db[h],
+ *                   dW <- dW' diag(gamma) + db beta^T (in place; db is already the gradient of b).
+ * Every reduction runs in a fixed order: equal inputs give bit-equal outputs.
+ * tests/test_gpu_batchnorm.py holds every kernel against float64 at the row and column counts where the launch geometry changes;
+ * tests/test_batchnorm_bounds_host.py checks its bounds on the CPU. */
+size_t uic_batchnorm_scratch_floats(int32_t NR, int32_t C);
+int uic_batchnorm_stats(int32_t in_dtype, const void* x, int32_t NR, int32_t R, int32_t C, const int32_t* row_len, float* part,
+                        float momentum, float eps, int32_t rep, float* stat, float* run_mean, float* run_var, void* stream);
+int uic_batchnorm_stats_running(const float* run_mean, const float* run_var, int32_t C, float eps, float* stat, void* stream);
+int uic_batchnorm_apply(int32_t in_dtype, int32_t out_dtype, const void* x, int32_t NR, int32_t R, int32_t C, const int32_t* row_len,
+                        const float* stat, const float* gamma, const float* beta, int32_t zero_padded, void* out, void* stream);
+int uic_batchnorm_backward(int32_t dtype, float* d, const void* y, int32_t NR, int32_t R, int32_t C, const int32_t* row_len,
+                           const float* stat, const float* gamma, int32_t training, float* part, float* red, float* dgamma,
+                           float* dbeta, void* stream);
+int uic_batchnorm_fold_weight(int32_t dtype, const float* W, const float* gamma, const float* beta, const float* b, int32_t H,
+                              int32_t D, void* Weff, float* beff, void* stream);
+int uic_batchnorm_fold_grad(const float* W, const float* gamma, const float* beta, float* dW, const float* db, int32_t H, int32_t D,
+                            float* dgamma, float* dbeta, void* stream);
+
 /* utilities */
 int uic_cast_from_f32(int32_t dtype, const float* src, void* dst, size_t n, void* stream);
 int uic_cast_to_f32(int32_t dtype, const void* src, float* dst, size_t n, void* stream);

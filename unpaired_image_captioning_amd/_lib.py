@@ -336,6 +336,16 @@ _SIGS = {
     "uic_xe_criterion": (C.c_int, [C.c_int32] * 5 + [C.c_void_p, C.c_void_p] + [C.c_void_p, C.c_int32, C.c_int32] * 2 + [C.c_void_p] +
                          [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p,
                                                                C.c_int32, C.POINTER(C.c_int32), C.c_void_p]),
+    "uic_batchnorm_scratch_floats": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "uic_batchnorm_stats": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float, C.c_float,
+                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uic_batchnorm_stats_running": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
+    "uic_batchnorm_apply": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 +
+                            [C.c_int32, C.c_void_p, C.c_void_p]),
+    "uic_batchnorm_backward": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 3 +
+                               [C.c_int32] + [C.c_void_p] * 5),
+    "uic_batchnorm_fold_weight": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "uic_batchnorm_fold_grad": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "uic_cast_from_f32": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uic_cast_to_f32": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uic_transpose": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),

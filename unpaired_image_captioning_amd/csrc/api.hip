@@ -352,6 +352,70 @@ int uic_xe_criterion(int32_t dtype, int32_t M, int32_t N, int32_t V1, int32_t ld
   return uic_xe_launch(x, (hipStream_t)stream, kernel_id);
 }
 
+// BatchNorm1d of att_embed on its own: argument checks here, the launchers of csrc/batchnorm.hip do the work
+#define UIC_BN_DTYPE(dt, who) UIC_REQUIRE((dt) == UIC_F32 || (dt) == UIC_BF16, who ": bad dtype %d", (int)(dt))
+#define UIC_BN_SHAPE(who)                                                                                        \
+  UIC_REQUIRE(NR > 0 && C > 0 && C % 4 == 0, who ": NR=%d C=%d (NR > 0, C a positive multiple of 4)", NR, C);   \
+  UIC_REQUIRE(!row_len || R > 0, who ": R=%d with a row_len", R)
+
+size_t uic_batchnorm_scratch_floats(int32_t NR, int32_t C) {
+  if (NR <= 0 || C <= 0 || C % 4 != 0) {
+    uic_set_error("batchnorm_scratch_floats: NR=%d C=%d (NR > 0, C a positive multiple of 4)", NR, C);
+    return 0;
+  }
+  return uic_bn_scratch_floats(NR, C);
+}
+
+int uic_batchnorm_stats(int32_t in_dtype, const void* x, int32_t NR, int32_t R, int32_t C, const int32_t* row_len, float* part,
+                        float momentum, float eps, int32_t rep, float* stat, float* run_mean, float* run_var, void* stream) {
+  UIC_BN_DTYPE(in_dtype, "batchnorm_stats");
+  UIC_REQUIRE(x && part && stat, "batchnorm_stats: null pointer");
+  UIC_BN_SHAPE("batchnorm_stats");
+  UIC_REQUIRE(rep >= 1, "batchnorm_stats: rep=%d must be >= 1", rep);
+  return uic_bn_stats_launch(in_dtype, x, NR, R, C, row_len, part, momentum, eps, stat, run_mean, run_var, (hipStream_t)stream, (float)rep);
+}
+
+int uic_batchnorm_stats_running(const float* run_mean, const float* run_var, int32_t C, float eps, float* stat, void* stream) {
+  UIC_REQUIRE(run_mean && run_var && stat, "batchnorm_stats_running: null pointer");
+  UIC_REQUIRE(C > 0 && C % 4 == 0, "batchnorm_stats_running: C=%d must be a positive multiple of 4", C);
+  return uic_bn_stats_running_launch(run_mean, run_var, C, eps, stat, (hipStream_t)stream);
+}
+
+int uic_batchnorm_apply(int32_t in_dtype, int32_t out_dtype, const void* x, int32_t NR, int32_t R, int32_t C, const int32_t* row_len,
+                        const float* stat, const float* gamma, const float* beta, int32_t zero_padded, void* out, void* stream) {
+  UIC_BN_DTYPE(in_dtype, "batchnorm_apply");
+  UIC_BN_DTYPE(out_dtype, "batchnorm_apply");
+  UIC_REQUIRE(x && stat && out, "batchnorm_apply: null pointer");
+  UIC_BN_SHAPE("batchnorm_apply");
+  return uic_bn_apply_launch(in_dtype, out_dtype, x, NR, R, C, row_len, stat, gamma, beta, zero_padded, out, (hipStream_t)stream);
+}
+
+int uic_batchnorm_backward(int32_t dtype, float* d, const void* y, int32_t NR, int32_t R, int32_t C, const int32_t* row_len,
+                           const float* stat, const float* gamma, int32_t training, float* part, float* red, float* dgamma,
+                           float* dbeta, void* stream) {
+  UIC_BN_DTYPE(dtype, "batchnorm_backward");
+  UIC_REQUIRE(d && y && stat && gamma && part && red, "batchnorm_backward: null pointer");
+  UIC_BN_SHAPE("batchnorm_backward");
+  return uic_bn_bwd_launch(dtype, d, y, NR, R, C, row_len, stat, gamma, training, part, red, dgamma, dbeta, (hipStream_t)stream);
+}
+
+int uic_batchnorm_fold_weight(int32_t dtype, const float* W, const float* gamma, const float* beta, const float* b, int32_t H,
+                              int32_t D, void* Weff, float* beff, void* stream) {
+  UIC_BN_DTYPE(dtype, "batchnorm_fold_weight");
+  UIC_REQUIRE(W && gamma && beta && b && Weff && beff, "batchnorm_fold_weight: null pointer");
+  UIC_REQUIRE(H > 0 && D > 0, "batchnorm_fold_weight: H=%d D=%d", H, D);
+  return uic_bn_fold_weight_launch(dtype, W, gamma, beta, b, H, D, Weff, beff, (hipStream_t)stream);
+}
+
+int uic_batchnorm_fold_grad(const float* W, const float* gamma, const float* beta, float* dW, const float* db, int32_t H, int32_t D,
+                            float* dgamma, float* dbeta, void* stream) {
+  UIC_REQUIRE(W && gamma && beta && dW && db && dgamma && dbeta, "batchnorm_fold_grad: null pointer");
+  UIC_REQUIRE(H > 0 && D > 0, "batchnorm_fold_grad: H=%d D=%d", H, D);
+  return uic_bn_fold_grad_launch(W, gamma, beta, dW, db, H, D, dgamma, dbeta, (hipStream_t)stream);
+}
+#undef UIC_BN_DTYPE
+#undef UIC_BN_SHAPE
+
 int uic_cast_from_f32(int32_t dtype, const float* src, void* dst, size_t n, void* stream) {
   return uic_cast_f32_launch(dtype, src, dst, n, (hipStream_t)stream);
 }
