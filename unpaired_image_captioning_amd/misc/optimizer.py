@@ -38,6 +38,8 @@ class FlatArena(object):
 
     def __init__(self, module, names=None, world=1, rank=0, pieces=None, operand_dtype=None):
         params = dict(module.named_parameters())
+        # module.parameters() in registration order: the order torch.optim.Adam numbers its state in (export / import below)
+        self.param_order = [(k, tuple(p.shape)) for k, p in params.items()]
         self.world, self.rank = int(world), int(rank)
         self.pieces, self.piece_names = [], []
         self.offsets = {}
@@ -273,6 +275,82 @@ class FlatArena(object):
                 exchange.all_gather(self.flat, *self.pieces[g])
         self.masters_stale = False
 
+    # ------------------------------------------------------------------ checkpoints ("Checkpoints")
+    def gather_moments(self, exchange):
+        """All-gather exp_avg / exp_avg_sq of every piece in place, as gather_masters does for `flat` (a collective: every rank
+        calls it): a rank's Adam moments exist only on its owned_ranges().  Afterwards the slices this rank does NOT own hold the
+        owners' moments of that moment; they go stale as training continues and nothing reads them -- Adam runs on owned_ranges()
+        only, and every export gathers again first."""
+        if self.pieces and exchange is not None and exchange.world_size > 1:
+            for buf in (self.exp_avg, self.exp_avg_sq):
+                for g in range(len(self.pieces)):
+                    exchange.all_gather(buf, *self.pieces[g])
+
+    def export_adam_state(self, lr, betas, eps, step, exchange=None, collect=True):
+        """The arena's Adam state in the layout of torch.optim.Adam.state_dict() over module.parameters() -- what the reference
+        saves (P/trainer.py:103-104) and reads back (P/misc/optimizer.py:80-87): entry i is the i-th parameter in REGISTRATION
+        order (not the arena's), state[i] = {'step', 'exp_avg', 'exp_avg_sq'} with host tensors of the parameter's shape.  A
+        parameter outside the arena keeps its index and gets no state; before the first step there is no state at all, as in
+        torch.  The param_groups keys are the installed torch's own, so torch.optim.Adam.load_state_dict takes the result.
+        Sharded arenas all-gather the moments first: a collective, every rank calls this; collect=False (a rank that writes no
+        file) stops there and returns None."""
+        self.gather_moments(exchange)
+        if not collect:
+            return None
+        return self.adam_state_from(self.exp_avg.detach().cpu(), self.exp_avg_sq.detach().cpu(), lr, betas, eps, step, clone=True)
+
+    def adam_state_from(self, m, v, lr, betas, eps, step, clone=False):
+        """export_adam_state's dict from host copies `m` / `v` of exp_avg / exp_avg_sq (at least the arena's first scalars_off
+        elements; Trainer's checkpoint snapshot hands in its pinned buffers).  clone=False: the state tensors are views of m / v."""
+        group = dict(torch.optim.Adam([torch.nn.Parameter(torch.zeros(1))]).state_dict()['param_groups'][0])
+        group.update(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=0,
+                     params=list(range(len(self.param_order))))
+        state = {}
+        if step > 0:
+            for i, (k, shape) in enumerate(self.param_order):
+                if k not in self.offsets:
+                    continue
+                o, n = self.offsets[k], self.params[k].numel()
+                em, ev = m[o:o + n].view(shape), v[o:o + n].view(shape)
+                state[i] = {'step': torch.tensor(float(step)), 'exp_avg': em.clone() if clone else em,
+                            'exp_avg_sq': ev.clone() if clone else ev}
+        return {'state': state, 'param_groups': [group]}
+
+    def import_adam_state(self, sd):
+        """Inverse of export_adam_state.  Entries are matched BY POSITION in the concatenated param_groups[*]['params'] -- torch 0.3
+        wrote id(p) there --, 'step' may be an int or a tensor.  Raises ValueError (nothing is written then) on a shape mismatch or
+        when the parameters' steps differ: the arena has one step.  The whole arena is filled on every rank, whatever world size
+        wrote the file; the operand-dtype copy is rebuilt from the masters (load the weights first) and masters_stale is cleared.
+        Returns (step, lr)."""
+        keys = [key for g in sd['param_groups'] for key in g['params']]
+        if len(keys) != len(self.param_order):
+            raise ValueError("optimizer state for %d parameters, the module has %d" % (len(keys), len(self.param_order)))
+        step, first, found = 0, None, []
+        for key, (k, shape) in zip(keys, self.param_order):
+            st = sd['state'].get(key)
+            if st is None or k not in self.offsets:
+                continue
+            for f in ('exp_avg', 'exp_avg_sq'):
+                if tuple(st[f].shape) != shape:
+                    raise ValueError("optimizer state %r (parameter %s): %s has shape %s, the parameter %s"
+                                     % (key, k, f, tuple(st[f].shape), shape))
+            s = int(st['step'].item()) if torch.is_tensor(st['step']) else int(st['step'])
+            if first is None:
+                step, first = s, (key, k)
+            elif s != step:
+                raise ValueError("optimizer state %r (parameter %s) is at step %d, %r (parameter %s) at step %d: the arena has one "
+                                 "step" % (key, k, s, first[0], first[1], step))
+            found.append((k, st))
+        self.exp_avg.zero_()
+        self.exp_avg_sq.zero_()
+        for k, st in found:
+            o, n = self.offsets[k], self.params[k].numel()
+            self.exp_avg[o:o + n].copy_(st['exp_avg'].reshape(-1))
+            self.exp_avg_sq[o:o + n].copy_(st['exp_avg_sq'].reshape(-1))
+        self.sync_operand_copy()
+        self.masters_stale = False
+        return step, float(sd['param_groups'][0]['lr'])
+
     def bind_grads(self):
         """Make every p.grad the arena view, so autograd accumulates in place."""
         for k, p in self.params.items():
@@ -468,6 +546,36 @@ class Optim(object):
             self.last_guard = guard
             self.nmt_arena.adam(self.nmt_current_lr, (self.nmt_optim_alpha, self.nmt_optim_beta), self.nmt_optim_epsilon,
                                 self._nmt_steps, nmt_grad_scale, self.nmt_max_grad_norm, guard=guard)
+
+    def state_dict(self, collect=True):
+        """Both arenas' Adam state (FlatArena.export_adam_state: the reference's optimizer_i2t / optimizer_nmt files, None for an
+        arena that was not built) plus what the reference keeps on the Optim object itself: the step counters and the current
+        learning rates.  A collective under the sharded exchange: every rank calls it (collect=False: a rank that writes no file
+        takes part in the gathers and gets None for the arenas)."""
+        a, n = self.i2t_arena, self.nmt_arena
+        return {'i2t': None if a is None else a.export_adam_state(self.i2t_current_lr, (self.i2t_optim_alpha, self.i2t_optim_beta),
+                                                                  self.i2t_optim_epsilon, self._i2t_steps, self.exchange, collect),
+                'nmt': None if n is None else n.export_adam_state(self.nmt_current_lr, (self.nmt_optim_alpha, self.nmt_optim_beta),
+                                                                  self.nmt_optim_epsilon, self._nmt_steps, self.exchange, collect),
+                **self.counters()}
+
+    def counters(self):
+        """The host part of state_dict: step counters and current learning rates.  Trainer.save_models stores exactly this dict in
+        trainer_state and writes the arenas' Adam state from its own snapshot buffers (FlatArena.adam_state_from); load_state_dict
+        takes the two together again."""
+        return {'_step': self._step, '_i2t_steps': self._i2t_steps, '_nmt_steps': self._nmt_steps,
+                'i2t_current_lr': float(self.i2t_current_lr), 'nmt_current_lr': float(self.nmt_current_lr)}
+
+    def load_state_dict(self, sd):
+        """Inverse of state_dict (after set_parameters and after the weights were loaded).  A dict that holds only the Adam state --
+        the reference's files on their own -- sets the counters and learning rates from the files' step and lr."""
+        for kind, arena in (('i2t', self.i2t_arena), ('nmt', self.nmt_arena)):
+            if arena is None or sd.get(kind) is None:
+                continue
+            step, lr = arena.import_adam_state(sd[kind])
+            setattr(self, '_%s_steps' % kind, int(sd.get('_%s_steps' % kind, step)))
+            setattr(self, '%s_current_lr' % kind, float(sd.get('%s_current_lr' % kind, lr)))
+        self._step = int(sd.get('_step', max(self._i2t_steps, self._nmt_steps)))
 
     def zero_grad(self, nmt_direct=False):
         """nmt_direct (Trainer.train_nmt): the coming backward pass is the in-place one (models/NMT_Models.py, _NmtStep.backward:
