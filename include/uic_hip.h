@@ -731,6 +731,52 @@ int uic_batchnorm_fold_weight(int32_t dtype, const float* W, const float* gamma,
 int uic_batchnorm_fold_grad(const float* W, const float* gamma, const float* beta, float* dW, const float* db, int32_t H, int32_t D,
                             float* dgamma, float* dbeta, void* stream);
 
+/* self.embed = nn.Embedding + ReLU + Dropout (P/models/AttModel.py:73-75,160) and its gradient on their own -- the embedding
+ * launches of the model steps (csrc/pointwise.hip), all T decode steps at once.
+ *   tokens  device int64, row-major [N, ld_tokens], ld_tokens >= T.  Rows of the embedded tensor are TIME-MAJOR: row = t * N + n
+ *           holds the token tokens[n * ld_tokens + t].  A token outside [0, V1) counts as token 0.  N, T >= 0, N * T < 2^30.
+ *   table / dtable  [V1, E] row-major, V1 > 0, E a positive multiple of 4.  dtable is f32.
+ *   out / xt / dxt  [T * N, E] row-major; dxt is f32.
+ *   dtypes are UIC_DTYPE_F32 / UIC_DTYPE_BF16.  A bf16 table gives bf16 outputs only.
+ *   alignment: f32 rows are read and written as float4 -- an f32 table, dxt, an f32 xt and dtable are 16-byte aligned; a bf16 table
+ *           and a bf16 xt are 8-byte aligned (four elements per load); out needs the alignment of its element only (bf16 outputs
+ *           with E % 8 == 0 and 16-byte aligned out and table take a kernel with one wave per row, the same bits otherwise);
+ *           scratch is 16-byte aligned.
+ * uic_embedding_forward: out[row, c] = cast(relu?(table[token, c]) * m), the arithmetic in f32, relu = 0 | 1, m the dropout factor
+ *   (0 or 1 / (1 - drop_p), drop_p in [0, 1), 1 when drop_p == 0) of element index idx_base + row * E + c TAKEN MODULO 2^32 at
+ *   (seed, site): exactly what uic_dropout_mask(n = T N E, drop_p, seed, site, base = idx_base) returns.
+ * uic_embedding_backward: dtable[v, :] = (1 / (1 - drop_p)) * sum over the rows whose token is v of dxt[row, :] masked by xt.
+ *   xt is the forward output (in `dtype`): an entry of dxt passes only where xt > 0, so ReLU and the dropped elements are ONE mask
+ *   (zero, negative zero, negatives and NaN do not pass); xt == NULL means no mask.  skip_token < 0: no padding index; otherwise
+ *   (skip_token < V1) that row of dtable is left as `prepare` zeroed it (nn.Embedding's padding_idx).  Rows of dtable that no
+ *   position selects are exactly 0.
+ * uic_embedding_backward_prepare / _gather: the same in two calls, so that the bucketing (which needs only the tokens) can run
+ *   before the gradients exist.  `prepare` ZEROES dtable and buckets the positions into `scratch`; `gather` adds the sums.
+ *   split = 0: one gather (half = 0) gives the whole gradient.  split in (0, T): the positions of decode steps [0, split) and
+ *   [split, T) are bucketed apart, gather(half = 0) ADDS the first share into dtable and gather(half = 1) the second, in either
+ *   order, each reading only its own rows of dxt / xt.  Both calls must get the same split (and N, T, V1, E, tokens, scratch).
+ *   uic_embedding_backward = prepare + gather with split = 0.
+ *   scratch  uic_embedding_scratch_ints(N, T, V1, E) int32 (0 = bad arguments; the size does not depend on split); it needs NO
+ *           initialisation, every slot that is read was written by the same prepare / gather.
+ * N == 0 or T == 0 is a successful no-op (prepare still zeroes dtable).  A refused call (non-zero return, uic_last_error_string)
+ * launches nothing.
+ * Every table row is STORED by one owner, its sum taken in a fixed order (a stable counting sort of the positions, no
+ * floating-point atomics): equal inputs give bit-equal outputs.
+ * tests/test_gpu_embedding.py holds both directions exactly (integer-valued gradients against float64) at the bucket sizes and
+ * counts where the launch geometry changes; tests/embedding_cases.py restates that geometry and
+ * tests/test_embedding_cases_host.py checks on the CPU that the cases reach every branch of it. */
+size_t uic_embedding_scratch_ints(int32_t N, int32_t T, int32_t V1, int32_t E);
+int uic_embedding_forward(int32_t out_dtype, const void* table, int32_t table_dtype, int32_t V1, int32_t E, const int64_t* tokens,
+                          int32_t ld_tokens, int32_t N, int32_t T, float drop_p, uint32_t seed, uint32_t site, size_t idx_base,
+                          int32_t relu, void* out, void* stream);
+int uic_embedding_backward_prepare(const int64_t* tokens, int32_t ld_tokens, int32_t N, int32_t T, int32_t V1, int32_t E, float* dtable,
+                                   int32_t* scratch, int32_t split, void* stream);
+int uic_embedding_backward_gather(int32_t dtype, const float* dxt, const void* xt, const int64_t* tokens, int32_t ld_tokens, int32_t N,
+                                  int32_t T, int32_t V1, int32_t E, float drop_p, int64_t skip_token, float* dtable, int32_t* scratch,
+                                  int32_t split, int32_t half, void* stream);
+int uic_embedding_backward(int32_t dtype, const float* dxt, const void* xt, const int64_t* tokens, int32_t ld_tokens, int32_t N, int32_t T,
+                           int32_t V1, int32_t E, float drop_p, int64_t skip_token, float* dtable, int32_t* scratch, void* stream);
+
 /* utilities */
 int uic_cast_from_f32(int32_t dtype, const float* src, void* dst, size_t n, void* stream);
 int uic_cast_to_f32(int32_t dtype, const void* src, float* dst, size_t n, void* stream);

@@ -346,6 +346,14 @@ _SIGS = {
                                [C.c_int32] + [C.c_void_p] * 5),
     "uic_batchnorm_fold_weight": (C.c_int, [C.c_int32] + [C.c_void_p] * 4 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
     "uic_batchnorm_fold_grad": (C.c_int, [C.c_void_p] * 5 + [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "uic_embedding_scratch_ints": (C.c_size_t, [C.c_int32] * 4),
+    "uic_embedding_forward": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
+                                        C.c_float, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int32, C.c_void_p, C.c_void_p]),
+    "uic_embedding_backward_prepare": (C.c_int, [C.c_void_p] + [C.c_int32] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "uic_embedding_backward_gather": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 +
+                                      [C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
+    "uic_embedding_backward": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 5 +
+                               [C.c_float, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uic_cast_from_f32": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uic_cast_to_f32": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uic_transpose": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),

@@ -416,6 +416,90 @@ int uic_batchnorm_fold_grad(const float* W, const float* gamma, const float* bet
 #undef UIC_BN_DTYPE
 #undef UIC_BN_SHAPE
 
+// nn.Embedding (+ ReLU + Dropout) forward and its bucketed backward on their own: argument checks here, the launchers of
+// csrc/pointwise.hip do the work.  The alignments are those of the kernels' vector loads: f32 rows are read and stored as float4,
+// a bf16 table and a bf16 xt as uint2; scratch holds the int4 loads of the scan and the float4 partial rows.
+#define UIC_EMB_DTYPE(dt, who) UIC_REQUIRE((dt) == UIC_F32 || (dt) == UIC_BF16, who ": bad dtype %d", (int)(dt))
+#define UIC_EMB_ALIGNED(p, bytes, who, name) \
+  UIC_REQUIRE(((uintptr_t)(p) & (uintptr_t)((bytes) - 1)) == 0, who ": " name " must be %d-byte aligned", (int)(bytes))
+#define UIC_EMB_SHAPE(who)                                                                                              \
+  UIC_REQUIRE(E > 0 && E % 4 == 0 && V1 > 0, who ": E=%d V1=%d (E a positive multiple of 4, V1 > 0)", E, V1);            \
+  UIC_REQUIRE(N >= 0 && T >= 0 && ld_tokens >= T, who ": N=%d T=%d ld_tokens=%d (N, T >= 0, ld_tokens >= T)", N, T, ld_tokens); \
+  UIC_REQUIRE((int64_t)N * T < ((int64_t)1 << 30), who ": N * T = %lld positions (< 2^30)", (long long)N * T)
+#define UIC_EMB_SPLIT(who) UIC_REQUIRE(split >= 0 && (split == 0 || split < T), who ": split=%d outside [0, T = %d)", split, T)
+
+size_t uic_embedding_scratch_ints(int32_t N, int32_t T, int32_t V1, int32_t E) {
+  if (N < 0 || T < 0 || V1 <= 0 || E <= 0 || E % 4 != 0 || (int64_t)N * T >= ((int64_t)1 << 30)) {
+    uic_set_error("embedding_scratch_ints: N=%d T=%d V1=%d E=%d (N, T >= 0, N * T < 2^30, V1 > 0, E a positive multiple of 4)", N, T, V1, E);
+    return 0;
+  }
+  return uic_embed_bwd_sorted_scratch_ints(N, T, V1, E);
+}
+
+int uic_embedding_forward(int32_t out_dtype, const void* table, int32_t table_dtype, int32_t V1, int32_t E, const int64_t* tokens,
+                          int32_t ld_tokens, int32_t N, int32_t T, float drop_p, uint32_t seed, uint32_t site, size_t idx_base,
+                          int32_t relu, void* out, void* stream) {
+  UIC_EMB_DTYPE(out_dtype, "embedding_forward");
+  UIC_EMB_DTYPE(table_dtype, "embedding_forward");
+  UIC_REQUIRE(!(table_dtype == UIC_BF16 && out_dtype == UIC_F32), "embedding_forward: a bf16 table needs bf16 outputs");
+  UIC_REQUIRE(table && tokens && out, "embedding_forward: null pointer");
+  UIC_EMB_SHAPE("embedding_forward");
+  UIC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "embedding_forward: drop_p=%g outside [0, 1)", (double)drop_p);
+  UIC_EMB_ALIGNED(table, table_dtype == UIC_BF16 ? 8 : 16, "embedding_forward", "table");
+  UIC_EMB_ALIGNED(out, out_dtype == UIC_BF16 ? 2 : 4, "embedding_forward", "out");
+  return uic_embed_fwd_t_launch(out_dtype, table, table_dtype, V1, E, tokens, ld_tokens, N, T, drop_p, seed, site, idx_base, relu, out,
+                                (hipStream_t)stream);
+}
+
+int uic_embedding_backward_prepare(const int64_t* tokens, int32_t ld_tokens, int32_t N, int32_t T, int32_t V1, int32_t E, float* dtable,
+                                   int32_t* scratch, int32_t split, void* stream) {
+  UIC_REQUIRE(tokens && dtable && scratch, "embedding_backward_prepare: null pointer");
+  UIC_EMB_SHAPE("embedding_backward_prepare");
+  UIC_EMB_SPLIT("embedding_backward_prepare");
+  UIC_EMB_ALIGNED(dtable, 16, "embedding_backward_prepare", "dtable");
+  UIC_EMB_ALIGNED(scratch, 16, "embedding_backward_prepare", "scratch");
+  return uic_embed_bwd_sorted_prepare(tokens, ld_tokens, N, T, V1, E, dtable, scratch, (hipStream_t)stream, split);
+}
+
+int uic_embedding_backward_gather(int32_t dtype, const float* dxt, const void* xt, const int64_t* tokens, int32_t ld_tokens, int32_t N,
+                                  int32_t T, int32_t V1, int32_t E, float drop_p, int64_t skip_token, float* dtable, int32_t* scratch,
+                                  int32_t split, int32_t half, void* stream) {
+  UIC_EMB_DTYPE(dtype, "embedding_backward_gather");
+  UIC_REQUIRE(dxt && tokens && dtable && scratch, "embedding_backward_gather: null pointer");
+  UIC_EMB_SHAPE("embedding_backward_gather");
+  UIC_EMB_SPLIT("embedding_backward_gather");
+  UIC_REQUIRE((half == 0 || half == 1) && !(half && split == 0), "embedding_backward_gather: half=%d with split=%d (0 or 1; 1 only with a split)",
+              half, split);
+  UIC_REQUIRE(skip_token < V1, "embedding_backward_gather: skip_token=%lld outside the table (V1=%d; < 0 = none)", (long long)skip_token, V1);
+  UIC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "embedding_backward_gather: drop_p=%g outside [0, 1)", (double)drop_p);
+  UIC_EMB_ALIGNED(dxt, 16, "embedding_backward_gather", "dxt");
+  UIC_EMB_ALIGNED(xt, dtype == UIC_BF16 ? 8 : 16, "embedding_backward_gather", "xt");
+  UIC_EMB_ALIGNED(dtable, 16, "embedding_backward_gather", "dtable");
+  UIC_EMB_ALIGNED(scratch, 16, "embedding_backward_gather", "scratch");
+  return uic_embed_bwd_sorted_gather(dtype, dxt, xt, tokens, ld_tokens, N, T, V1, E, drop_p, (long)skip_token, dtable, scratch,
+                                     (hipStream_t)stream, split, half);
+}
+
+int uic_embedding_backward(int32_t dtype, const float* dxt, const void* xt, const int64_t* tokens, int32_t ld_tokens, int32_t N, int32_t T,
+                           int32_t V1, int32_t E, float drop_p, int64_t skip_token, float* dtable, int32_t* scratch, void* stream) {
+  // (every check before the first launch: a refused call leaves dtable as it was)
+  UIC_EMB_DTYPE(dtype, "embedding_backward");
+  UIC_REQUIRE(dxt && tokens && dtable && scratch, "embedding_backward: null pointer");
+  UIC_EMB_SHAPE("embedding_backward");
+  UIC_REQUIRE(skip_token < V1, "embedding_backward: skip_token=%lld outside the table (V1=%d; < 0 = none)", (long long)skip_token, V1);
+  UIC_REQUIRE(drop_p >= 0.f && drop_p < 1.f, "embedding_backward: drop_p=%g outside [0, 1)", (double)drop_p);
+  UIC_EMB_ALIGNED(dxt, 16, "embedding_backward", "dxt");
+  UIC_EMB_ALIGNED(xt, dtype == UIC_BF16 ? 8 : 16, "embedding_backward", "xt");
+  UIC_EMB_ALIGNED(dtable, 16, "embedding_backward", "dtable");
+  UIC_EMB_ALIGNED(scratch, 16, "embedding_backward", "scratch");
+  return uic_embed_bwd_sorted_launch(dtype, dxt, xt, tokens, ld_tokens, N, T, V1, E, drop_p, (long)skip_token, dtable, scratch,
+                                     (hipStream_t)stream);
+}
+#undef UIC_EMB_DTYPE
+#undef UIC_EMB_ALIGNED
+#undef UIC_EMB_SHAPE
+#undef UIC_EMB_SPLIT
+
 int uic_cast_from_f32(int32_t dtype, const float* src, void* dst, size_t n, void* stream) {
   return uic_cast_f32_launch(dtype, src, dst, n, (hipStream_t)stream);
 }
