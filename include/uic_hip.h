@@ -592,9 +592,59 @@ int uic_lstm_cell_fwd(int32_t dtype, int32_t M, int32_t H, int32_t nx, const voi
                       const float* b_ih, const float* b_hh, const float* c_prev, float* c_out, void* h_out,
                       void* gates_out, void* stream);
 /* Pointwise backward of the cell: dh [M,H] f32, dc [M,H] f32 (in: from the future, out: for the past),
- * gates (activated), c_prev, c  ->  dgates [M,4H] operand dtype. */
+ * gates (activated), c_prev, c  ->  dgates [M,4H] operand dtype.  uic_lstm_cell_bwd_sources with dh as its only source. */
 int uic_lstm_cell_bwd(int32_t dtype, int32_t M, int32_t H, const float* dh, float* dc, const void* gates,
                       const float* c_prev, const float* c, void* dgates, void* stream);
+
+/* The cell-backward launches of the BPTT chains on their own (backward of nn.LSTMCell, P/models/AttModel.py:434,441, of the NMT
+ * encoder / decoder cells and of the maxout LSTMCore, P/models/FCModel_NMT.py:32-50), with every d h source the model steps pass.
+ * Gates are STORED ACTIVATED (i, f, g, o), [M, 4H] row-major in `dtype` (UIC_DTYPE_F32 / UIC_DTYPE_BF16); everything else is f32.
+ *   dh  = drop(dh0) + dh1 + dh2 + sum_z slabA[z] + sum_z slabB[z]          tc = tanh(c)
+ *   dc' = dc + dh go (1 - tc^2)
+ *   dgates = { dc' gg gi (1 - gi),  dc' c_prev gf (1 - gf),  dc' gi (1 - gg^2),  dh tc go (1 - go) }      dc <- dc' gf   (IN PLACE)
+ * uic_lstm_cell_bwd_sources:
+ *   dh0 / dh1 / dh2  optional (NULL: absent) f32, element (m, u) at dhX[m * lddhX + u], lddhX >= H: a column block of a wider
+ *           buffer is passed as its first element and the buffer's row stride.  dh0 alone is multiplied by the dropout factor of
+ *           element index m * H + u at (seed, site) -- what uic_dropout_mask(n = M H, drop_p, seed, site, base = 0) returns;
+ *           drop_p in [0, 1), 0 = none.
+ *   slabA / slabB  split-K partial slabs (uic_linear_partials): nX >= 0 slices (0: absent, the pointer is not read), element
+ *           (z, m, u) at slabX[z * strideX + m * ldX + u], ldX >= H, summed in the order z = 0, 1, ...
+ *   c_prev  optional (NULL: d forget gate = 0);  c, dc [M, H] contiguous;  dgates [M, 4H] out, must not overlap an input.
+ *   M == 0 is a successful no-op; H > 0.  A refused call (non-zero return, uic_last_error_string) launches nothing.
+ *   One of three kernels runs; *kernel_id (host, optional) receives which.  Four hidden units per lane (UIC_LSTM_BWD_VEC4*) when
+ *   M H >= 65536, H % 4 == 0, M <= 65535, nA <= 4 and nB <= 4, every f32 operand that is present 16-byte aligned with its leading
+ *   dimension and slice stride a multiple of 4, gates and dgates 8-byte (bf16) / 16-byte (f32) aligned, and every f32 operand
+ *   ends below byte offset 2^31 - 16 from its own base (the kernel reads them with 32-bit buffer offsets); one unit per lane with
+ *   64-bit addressing (UIC_LSTM_BWD_SCALAR) otherwise.  The same formulas in all three; equal inputs give bit-equal outputs.
+ * uic_maxout_lstm_cell_bwd: gates and dgates are [M, 5H] = (in, forget, out, g = max(a, b), first = 1 where a was the larger);
+ *   dh = drop(dh0 + dh1) -- the dropped next_h is both the output and the recurrent state --;  dgates = { dc' g gi (1 - gi),
+ *   dc' c_prev gf (1 - gf), dh tc go (1 - go), first ? dc' gi : 0, first ? 0 : dc' gi };  one kernel, one unit per lane.
+ * uic_h2att_cell_bwd: the h2att input-gradient GEMM and the att_lstm cell backward of a BPTT step in ONE launch (backward of
+ *   P/models/AttModel.py:543 and :434; csrc/bptt_fused.hip): dh = datth [N, A] h2attT [H, A]^T + the two slab sources, no dh0 / dh1
+ *   / dh2 and no dropout.  bf16 only, H % 32 == 0, A in {128, 256, 512}, nA <= 4 and nB <= 4, datth / h2attT / c / c_prev / dc and
+ *   the slabs 16-byte aligned, gates / dgates 8-byte aligned, ldX and strideX multiples of 4; anything else is REFUSED with the
+ *   library's error (the model step then runs the GEMM and uic_lstm_cell_bwd_sources' kernels as two launches).  Rows are
+ *   processed in tiles of 32: rows >= N of dgates and dc are never written and no operand is read behind its row N - 1.
+ *   N == 0 is a successful no-op.
+ * tests/test_gpu_lstm_cell.py holds every kernel against float64, element by element, on both sides of each condition above;
+ * tests/lstm_cell_cases.py restates the choice of kernel and tests/test_lstm_cell_cases_host.py checks the cases and the bound on
+ * the CPU. */
+#define UIC_LSTM_BWD_SCALAR 0       /* lstm_bwd_kernel: one hidden unit per lane */
+#define UIC_LSTM_BWD_VEC4 1         /* lstm_bwd_vec4_kernel<T, false>: four units per lane, any set of sources */
+#define UIC_LSTM_BWD_VEC4_SIMPLE 2  /* lstm_bwd_vec4_kernel<T, true>: dh0 and c_prev present, dh1 / dh2 absent */
+int uic_lstm_cell_bwd_sources(int32_t dtype, int32_t M, int32_t H, const float* dh0, int32_t lddh0, float drop_p, uint32_t seed,
+                              uint32_t site, const float* dh1, int32_t lddh1, const float* dh2, int32_t lddh2,
+                              const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                              const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                              float* dc, const void* gates, const float* c_prev, const float* c, void* dgates,
+                              int32_t* kernel_id, void* stream);
+int uic_maxout_lstm_cell_bwd(int32_t dtype, int32_t M, int32_t H, const float* dh0, int32_t lddh0, const float* dh1, int32_t lddh1,
+                             float drop_p, uint32_t seed, uint32_t site, float* dc, const void* gates, const float* c_prev,
+                             const float* c, void* dgates, void* stream);
+int uic_h2att_cell_bwd(int32_t dtype, int32_t N, int32_t H, int32_t A, const void* datth, const void* h2attT,
+                       const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                       const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                       float* dc, const void* gates, const float* c_prev, const float* c, void* dgates, void* stream);
 
 /* Attention.forward after h2att (P/models/AttModel.py:544-556). */
 int uic_attention_fwd(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,

@@ -30,6 +30,7 @@ STEP_MARKS = 11          # UIC_STEP_MARKS
 
 
 XE_GENERIC, XE_LDS, XE_REG, XE_REG_WIDE, XE_BIG = 0, 1, 2, 3, 4     # UIC_XE_*: the kernel uic_xe_criterion launched
+LSTM_BWD_SCALAR, LSTM_BWD_VEC4, LSTM_BWD_VEC4_SIMPLE = 0, 1, 2      # UIC_LSTM_BWD_*: the kernel uic_lstm_cell_bwd_sources launched
 XE_KERNEL_NAMES = ("xe_kernel", "xe_lds_kernel", "xe_reg_kernel", "xe_reg_wide_kernel", "xe_big_kernel")
 
 MAX_LOGIT_LAYERS = 4
@@ -320,6 +321,13 @@ _SIGS = {
     "uic_lstm_cell_fwd": (C.c_int, [C.c_int32] * 4 + [C.POINTER(C.c_void_p), C.POINTER(C.c_int32), C.POINTER(C.c_void_p),
                                     C.POINTER(C.c_int32)] + [C.c_void_p] * 9),
     "uic_lstm_cell_bwd": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 7),
+    "uic_lstm_cell_bwd_sources": (C.c_int, [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_float, C.c_uint32, C.c_uint32] +
+                                  [C.c_void_p, C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.c_int32, C.c_size_t] * 2 + [C.c_void_p] * 5 +
+                                  [C.POINTER(C.c_int32), C.c_void_p]),
+    "uic_maxout_lstm_cell_bwd": (C.c_int, [C.c_int32] * 3 + [C.c_void_p, C.c_int32] * 2 + [C.c_float, C.c_uint32, C.c_uint32] +
+                                 [C.c_void_p] * 6),
+    "uic_h2att_cell_bwd": (C.c_int, [C.c_int32] * 4 + [C.c_void_p] * 2 + [C.c_void_p, C.c_int32, C.c_int32, C.c_size_t] * 2 +
+                           [C.c_void_p] * 6),
     "uic_attention_fwd": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 9),
     "uic_attention_bwd_step": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 9),
     "uic_attention_bwd_accum": (C.c_int, [C.c_int32] * 6 + [C.c_void_p] * 10),

@@ -179,13 +179,53 @@ int uic_lstm_cell_fwd(int32_t dtype, int32_t M, int32_t H, int32_t nx, const voi
   return uic_gemm_launch(g, (hipStream_t)stream);
 }
 
-int uic_lstm_cell_bwd(int32_t dtype, int32_t M, int32_t H, const float* dh, float* dc, const void* gates,
-                      const float* c_prev, const float* c, void* dgates, void* stream) {
+int uic_lstm_cell_bwd_sources(int32_t dtype, int32_t M, int32_t H, const float* dh0, int32_t lddh0, float drop_p, uint32_t seed,
+                              uint32_t site, const float* dh1, int32_t lddh1, const float* dh2, int32_t lddh2,
+                              const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                              const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                              float* dc, const void* gates, const float* c_prev, const float* c, void* dgates,
+                              int32_t* kernel_id, void* stream) {
+  UIC_REQUIRE(dtype == UIC_F32 || dtype == UIC_BF16, "lstm_cell_bwd_sources: dtype=%d", dtype);
   UicLstmBwdParams p;
   memset(&p, 0, sizeof(p));
-  p.dtype = dtype; p.M = M; p.H = H; p.dh0 = dh; p.lddh0 = H; p.dc = dc; p.gates = gates; p.c_prev = c_prev; p.c = c;
-  p.dgates = dgates;
-  return uic_lstm_bwd_launch(p, (hipStream_t)stream);
+  p.dtype = dtype; p.M = M; p.H = H;
+  p.dh0 = dh0; p.lddh0 = lddh0; p.drop_p = drop_p; p.seed = seed; p.site = site;
+  p.dh1 = dh1; p.lddh1 = lddh1; p.dh2 = dh2; p.lddh2 = lddh2;
+  p.slabA = slabA; p.ldA = ldA; p.nA = nA; p.strideA = strideA;
+  p.slabB = slabB; p.ldB = ldB; p.nB = nB; p.strideB = strideB;
+  p.dc = dc; p.gates = gates; p.c_prev = c_prev; p.c = c; p.dgates = dgates;
+  return uic_lstm_bwd_launch(p, (hipStream_t)stream, kernel_id);
+}
+
+int uic_lstm_cell_bwd(int32_t dtype, int32_t M, int32_t H, const float* dh, float* dc, const void* gates,
+                      const float* c_prev, const float* c, void* dgates, void* stream) {
+  return uic_lstm_cell_bwd_sources(dtype, M, H, dh, H, 0.f, 0, 0, nullptr, 0, nullptr, 0, nullptr, 0, 0, 0, nullptr, 0, 0, 0, dc, gates,
+                                   c_prev, c, dgates, nullptr, stream);
+}
+
+int uic_maxout_lstm_cell_bwd(int32_t dtype, int32_t M, int32_t H, const float* dh0, int32_t lddh0, const float* dh1, int32_t lddh1,
+                             float drop_p, uint32_t seed, uint32_t site, float* dc, const void* gates, const float* c_prev,
+                             const float* c, void* dgates, void* stream) {
+  UIC_REQUIRE(dtype == UIC_F32 || dtype == UIC_BF16, "maxout_lstm_cell_bwd: dtype=%d", dtype);
+  UicLstmBwdParams p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = dtype; p.M = M; p.H = H;
+  p.dh0 = dh0; p.lddh0 = lddh0; p.dh1 = dh1; p.lddh1 = lddh1; p.drop_p = drop_p; p.seed = seed; p.site = site;
+  p.dc = dc; p.gates = gates; p.c_prev = c_prev; p.c = c; p.dgates = dgates;
+  return uic_maxout_lstm_bwd_launch(p, (hipStream_t)stream);
+}
+
+int uic_h2att_cell_bwd(int32_t dtype, int32_t N, int32_t H, int32_t A, const void* datth, const void* h2attT,
+                       const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                       const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                       float* dc, const void* gates, const float* c_prev, const float* c, void* dgates, void* stream) {
+  UicH2attCellParams p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = dtype; p.N = N; p.H = H; p.A = A; p.datth = datth; p.h2attT = h2attT;
+  p.slabA = slabA; p.ldA = ldA; p.nA = nA; p.strideA = strideA;
+  p.slabB = slabB; p.ldB = ldB; p.nB = nB; p.strideB = strideB;
+  p.dc = dc; p.gates = gates; p.c_prev = c_prev; p.c = c; p.dgates = dgates;
+  return uic_h2att_cell_bwd_launch(p, (hipStream_t)stream);
 }
 
 int uic_attention_fwd(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,

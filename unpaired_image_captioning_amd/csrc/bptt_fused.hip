@@ -158,6 +158,10 @@ bool uic_h2att_cell_bwd_eligible(const UicH2attCellParams& p) {
 
 int uic_h2att_cell_bwd_launch(const UicH2attCellParams& p, hipStream_t s) {
   UIC_REQUIRE(p.datth && p.h2attT && p.gates && p.c && p.dc && p.dgates, "h2att_cell_bwd: null pointer");
+  UIC_REQUIRE(p.N >= 0 && p.H > 0 && p.A > 0, "h2att_cell_bwd: N=%d must be >= 0, H=%d and A=%d > 0", p.N, p.H, p.A);
+  UIC_REQUIRE((!p.nA || p.slabA) && (!p.nB || p.slabB) && p.nA >= 0 && p.nB >= 0 && (!p.nA || p.ldA >= p.H) && (!p.nB || p.ldB >= p.H),
+              "h2att_cell_bwd: slab sources");
+  if (p.N == 0) return UIC_OK;
   UIC_REQUIRE(uic_h2att_cell_bwd_eligible(p), "h2att_cell_bwd: shape not eligible (bf16, H %% 32 == 0, A in {128, 256, 512})");
   const dim3 grid((unsigned)((p.N + FT - 1) / FT), (unsigned)(p.H / FT));
   switch (p.A / 128) {

@@ -1525,23 +1525,43 @@ int uic_relu_mask_bwd_fold_launch(int dtype, const float* grad, const void* act,
   UIC_LAUNCH_CHECK("relu_mask_bwd_fold");
   return UIC_OK;
 }
-int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s) {
-  UIC_REQUIRE(p.dc && p.gates && p.c && p.dgates, "lstm_bwd: null pointer");
-  UIC_REQUIRE((!p.nA || p.slabA) && (!p.nB || p.slabB) && p.nA >= 0 && p.nB >= 0, "lstm_bwd: slab sources");
+// What both cell-backward launchers check before anything is launched (the kernels take all of it on trust).
+static int lstm_bwd_check(const UicLstmBwdParams& p, const char* who) {
+  UIC_REQUIRE(p.dc && p.gates && p.c && p.dgates, "%s: null pointer", who);
+  UIC_REQUIRE(p.M >= 0 && p.H > 0, "%s: M=%d must be >= 0 and H=%d > 0", who, p.M, p.H);
+  UIC_REQUIRE((!p.nA || p.slabA) && (!p.nB || p.slabB) && p.nA >= 0 && p.nB >= 0, "%s: slab sources", who);
+  UIC_REQUIRE((!p.dh0 || p.lddh0 >= p.H) && (!p.dh1 || p.lddh1 >= p.H) && (!p.dh2 || p.lddh2 >= p.H) && (!p.nA || p.ldA >= p.H) &&
+              (!p.nB || p.ldB >= p.H), "%s: a leading dimension below H=%d (lddh %d %d %d, ldA %d, ldB %d)", who, p.H, p.lddh0, p.lddh1,
+              p.lddh2, p.ldA, p.ldB);
+  UIC_REQUIRE(p.drop_p >= 0.f && p.drop_p < 1.f, "%s: drop_p=%f outside [0, 1)", who, (double)p.drop_p);
+  return UIC_OK;
+}
+int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kernel_id) {
+  UIC_TRY(lstm_bwd_check(p, "lstm_bwd"));
+  if (kernel_id) *kernel_id = UIC_LSTM_BWD_SCALAR;
   if (p.M == 0) return UIC_OK;
   auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
   // (small problems -- the pivot NMT's 64 rows -- keep one unit per lane: four times the workgroups, measured faster there)
   const bool vec = (size_t)p.M * p.H >= 65536 && p.H % 4 == 0 && al16(p.dc) && al16(p.c) && (!p.c_prev || al16(p.c_prev)) &&
                    ((uintptr_t)p.gates & 7) == 0 && ((uintptr_t)p.dgates & 7) == 0 && (p.dtype == UIC_BF16 || (al16(p.gates) && al16(p.dgates))) &&
                    (!p.dh0 || (al16(p.dh0) && p.lddh0 % 4 == 0)) && (!p.dh1 || (al16(p.dh1) && p.lddh1 % 4 == 0)) &&
-                   (!p.dh2 || (al16(p.dh2) && p.lddh2 % 4 == 0)) && (size_t)p.M * p.H < ((size_t)1 << 32) && p.M <= 65535 &&
+                   (!p.dh2 || (al16(p.dh2) && p.lddh2 % 4 == 0)) && p.M <= 65535 &&
                    p.nA <= 4 && p.nB <= 4 && (!p.nA || (al16(p.slabA) && p.ldA % 4 == 0 && p.strideA % 4 == 0)) &&
                    (!p.nB || (al16(p.slabB) && p.ldB % 4 == 0 && p.strideB % 4 == 0));
-  if (vec) {
+  // The vec4 kernel's f32 loads are raw buffer loads: 0x7fffffff records and a 32-bit BYTE offset, so a source whose last byte
+  // lies at 2^31 or beyond would be read as zeros (and past 2^32 from a wrapped address).  Such a source keeps the scalar
+  // kernel, which addresses with 64 bits.  span: floats from a source's base to the end of its last row (of its last slice).
+  auto span = [&](int ld, int n, size_t stride) { return (size_t)(n - 1) * stride + (size_t)(p.M - 1) * (size_t)ld + (size_t)p.H; };
+  auto fits = [](size_t floats) { return floats <= (((size_t)1 << 31) - 16) / 4; };
+  const bool near = fits((size_t)p.M * p.H) && (!p.dh0 || fits(span(p.lddh0, 1, 0))) && (!p.dh1 || fits(span(p.lddh1, 1, 0))) &&
+                    (!p.dh2 || fits(span(p.lddh2, 1, 0))) && (!p.nA || fits(span(p.ldA, p.nA, p.strideA))) &&
+                    (!p.nB || fits(span(p.ldB, p.nB, p.strideB)));
+  if (vec && near) {
     const int h4 = p.H / 4;
     const int bt = h4 >= NT ? NT : ((h4 + 63) / 64) * 64;
     const dim3 g4((unsigned)((h4 + bt - 1) / bt), (unsigned)p.M);
     const bool simple = p.dh0 && !p.dh1 && !p.dh2 && p.c_prev;
+    if (kernel_id) *kernel_id = simple ? UIC_LSTM_BWD_VEC4_SIMPLE : UIC_LSTM_BWD_VEC4;
     if (simple) {
       DISPATCH_T(p.dtype, hipLaunchKernelGGL((lstm_bwd_vec4_kernel<bf16_t, true>), g4, dim3(bt), 0, s, p),
                  hipLaunchKernelGGL((lstm_bwd_vec4_kernel<float, true>), g4, dim3(bt), 0, s, p));
@@ -1806,7 +1826,8 @@ int uic_sample_step_launch(const UicSampleParams& p, hipStream_t s) {
   return UIC_OK;
 }
 int uic_maxout_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s) {
-  UIC_REQUIRE(p.dc && p.gates && p.c && p.dgates, "maxout_lstm_bwd: null pointer");
+  UIC_TRY(lstm_bwd_check(p, "maxout_lstm_bwd"));
+  UIC_REQUIRE(!p.dh2 && !p.nA && !p.nB, "maxout_lstm_bwd: takes dh0 and dh1 only");
   if (p.M == 0) return UIC_OK;
   const int g = grid_for((size_t)p.M * p.H, NT);
   DISPATCH_T(p.dtype, hipLaunchKernelGGL(maxout_lstm_bwd_kernel<bf16_t>, dim3(g), dim3(NT), 0, s, p),

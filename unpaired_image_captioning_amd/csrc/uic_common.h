@@ -613,7 +613,7 @@ struct UicLstmBwdParams {
   const float* dh0; int lddh0;   // up to three dh sources (null = absent)
   const float* dh1; int lddh1;
   const float* dh2; int lddh2;
-  float drop_p; unsigned seed; unsigned site; size_t drop_base;  // dropout applied to dh0 only (out-dropout)
+  float drop_p; unsigned seed; unsigned site;   // dropout applied to dh0 only (out-dropout), element index m * H + u
   // two more dh sources given as split-K partial slabs (uic_linear_partials): dh += sum_z slabX[z * strideX + m * ldX + u]
   const float* slabA; int ldA, nA; size_t strideA;
   const float* slabB; int ldB, nB; size_t strideB;
@@ -623,7 +623,8 @@ struct UicLstmBwdParams {
   const float* c;                // [M,H]
   void* dgates;                  // [M,4H] operand dtype out
 };
-int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s);
+// kernel_id (host, optional): which kernel ran (UIC_LSTM_BWD_SCALAR / _VEC4 / _VEC4_SIMPLE, include/uic_hip.h)
+int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kernel_id = nullptr);
 // d h = d att_h[N, A] h2attT[H, A]^T + the two slab sources, then the nn.LSTMCell backward of UicLstmBwdParams -- the `h2att`
 // input-gradient GEMM and the att_lstm cell backward of a BPTT step in ONE launch (bptt_fused.hip; bf16)
 struct UicH2attCellParams {
