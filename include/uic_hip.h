@@ -782,7 +782,7 @@ int uic_batchnorm_fold_grad(const float* W, const float* gamma, const float* bet
                             float* dgamma, float* dbeta, void* stream);
 
 /* self.embed = nn.Embedding + ReLU + Dropout (P/models/AttModel.py:73-75,160) and its gradient on their own -- the embedding
- * launches of the model steps (csrc/pointwise.hip), all T decode steps at once.
+ * launches of the model steps (csrc/embedding.hip), all T decode steps at once.
  *   tokens  device int64, row-major [N, ld_tokens], ld_tokens >= T.  Rows of the embedded tensor are TIME-MAJOR: row = t * N + n
  *           holds the token tokens[n * ld_tokens + t].  A token outside [0, V1) counts as token 0.  N, T >= 0, N * T < 2^30.
  *   table / dtable  [V1, E] row-major, V1 > 0, E a positive multiple of 4.  dtable is f32.

@@ -1,4 +1,4 @@
-"""Token sets for the embedding kernels (csrc/pointwise.hip: embed_fwd_*, embed_hist / _block_prefix / _scan / _fill / _gather /
+"""Token sets for the embedding kernels (csrc/embedding.hip: embed_fwd_*, embed_hist / _block_prefix / _scan / _fill / _gather /
 _gather_finish behind uic_embedding_*), the launch geometry of those kernels restated, a classifier that says which branches of
 that geometry a token set reaches, and a plain numpy restatement of the bucketed sum -- shared by tests/test_embedding_cases_host.py
 (the cases reach every class; the restatement equals index_add_) and tests/test_gpu_embedding.py (the kernels themselves).

@@ -1,4 +1,4 @@
-"""Cases, float64 reference, per-element bound and kernel-choice classifier for the LSTM cell backward kernels (csrc/pointwise.hip:
+"""Cases, float64 reference, per-element bound and kernel-choice classifier for the LSTM cell backward kernels (csrc/lstm_cell.hip:
 lstm_bwd_kernel, lstm_bwd_vec4_kernel<T, SIMPLE>, maxout_lstm_bwd_kernel; csrc/bptt_fused.hip: h2att_cell_bwd_kernel<KS>) behind
 uic_lstm_cell_bwd_sources, uic_maxout_lstm_cell_bwd and uic_h2att_cell_bwd -- shared by tests/test_lstm_cell_cases_host.py (the cases
 reach every kernel and both sides of every condition of the choice; a float32 restatement of the kernels' formulas stays inside a
@@ -107,7 +107,7 @@ def layout(case, dtype):
     return out
 
 
-# ---- which kernel the launcher picks (csrc/pointwise.hip uic_lstm_bwd_launch; csrc/bptt_fused.hip uic_h2att_cell_bwd_eligible) ----
+# ---- which kernel the launcher picks (csrc/lstm_cell.hip uic_lstm_bwd_launch; csrc/bptt_fused.hip uic_h2att_cell_bwd_eligible) ----
 CELL_CONDITIONS = ("size", "h4", "rows", "nA", "nB", "near", "dc_al", "c_al", "c_prev_al", "gates_al", "dgates_al",
                    "dh0_al", "dh0_ld", "dh1_al", "dh1_ld", "dh2_al", "dh2_ld", "slabA_al", "slabA_ld", "slabA_stride", "slabB_al", "slabB_ld",
                    "slabB_stride")

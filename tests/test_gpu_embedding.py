@@ -1,4 +1,4 @@
-"""The embedding kernels behind uic_embedding_* (csrc/pointwise.hip: embed_fwd_kernel, embed_fwd_rows_bf16_kernel, and the backward
+"""The embedding kernels behind uic_embedding_* (csrc/embedding.hip: embed_fwd_kernel, embed_fwd_rows_bf16_kernel, and the backward
 pipeline embed_hist -> embed_block_prefix -> embed_scan -> embed_fill -> embed_gather -> embed_gather_finish) on their own, through
 raw pointers, on token sets shaped like captions: hot buckets of 17 to 200 and more entries back to back in the sorted list.
 

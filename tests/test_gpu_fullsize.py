@@ -257,7 +257,7 @@ def test_full_size_benchmark_dropout_step_vs_oracle(case, case_drop, dtype):
 def test_training_step_is_bit_reproducible(case, dtype, mode):
     """The same 640-row step three times with training-mode dropout (fixed seed): the loss and EVERY gradient tensor bit for
     bit -- incl. `embed.0.weight`, the backward of nn.Embedding (P/models/AttModel.py:73-75,160), which is a stable counting sort
-    of the token positions with one owner per table row (csrc/pointwise.hip), not floating-point atomics.  The padding token 0
+    of the token positions with one owner per table row (csrc/embedding.hip), not floating-point atomics.  The padding token 0
     owns thousands of positions here (a bucket that straddles many gather workgroups) and most words one or two."""
     from unpaired_image_captioning_amd.trainer import xe_step
     W, b, *_ = case

@@ -1,5 +1,5 @@
 """The LSTM cell backward kernels on their own, through raw pointers: lstm_bwd_kernel, lstm_bwd_vec4_kernel<T, SIMPLE> (both
-variants) and maxout_lstm_bwd_kernel (csrc/pointwise.hip) behind uic_lstm_cell_bwd_sources / uic_maxout_lstm_cell_bwd, and
+variants) and maxout_lstm_bwd_kernel (csrc/lstm_cell.hip) behind uic_lstm_cell_bwd_sources / uic_maxout_lstm_cell_bwd, and
 h2att_cell_bwd_kernel<KS> (csrc/bptt_fused.hip; the kernel of the benchmarked step) behind uic_h2att_cell_bwd.
 
 Every case (tests/lstm_cell_cases.py; tests/test_lstm_cell_cases_host.py shows on the CPU what the list reaches) checks

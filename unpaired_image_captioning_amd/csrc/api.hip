@@ -21,88 +21,17 @@ int uic_check_hip(hipError_t e, const char* what) {
   return (int)e > 0 ? (int)e : 1;
 }
 
-namespace {
-// LanguageModelCriterion on materialised log-probs (P/misc/criterion.py:143-150)
-__global__ void lm_crit_rows_kernel(int N, int T, int V1, const float* logp, const int64_t* target, int ldt,
-                                    const float* mask, int ldm, float* row_loss, float* row_mask) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N * T) return;
-  const int n = i / T, t = i - n * T;
-  long y = target[(size_t)n * ldt + t];
-  if (y < 0 || y >= V1) y = 0;
-  const float m = mask[(size_t)n * ldm + t];
-  row_loss[i] = -logp[((size_t)n * T + t) * V1 + y] * m;
-  row_mask[i] = m;
+// UicAdamParams of one optimizer step: the bias corrections 1 - beta^step in double, as torch.optim.Adam computes them
+static UicAdamParams adam_params(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
+                                 int32_t step, float grad_scale, float max_norm, const float* sqnorm, const int32_t* guard) {
+  UicAdamParams a;
+  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
+  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
+  a.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
+  a.grad_scale = grad_scale;
+  a.max_norm = max_norm; a.sqnorm = sqnorm; a.guard = guard;
+  return a;
 }
-__global__ void lm_crit_final_kernel(const float* row_loss, const float* row_mask, int n, float* out) {
-  __shared__ float s_a[256], s_b[256];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < n; i += 256) { a += row_loss[i]; b += row_mask[i]; }
-  s_a[threadIdx.x] = a; s_b[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { s_a[threadIdx.x] += s_a[threadIdx.x + o]; s_b[threadIdx.x] += s_b[threadIdx.x + o]; }
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) { out[0] = s_a[0] / s_b[0]; out[1] = s_b[0]; }
-}
-__global__ void lm_crit_bwd_kernel(int N, int T, int V1, const int64_t* target, int ldt, const float* mask, int ldm,
-                                   const float* loss_den, float grad_out, float* dlogp) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= N * T) return;
-  const int n = i / T, t = i - n * T;
-  long y = target[(size_t)n * ldt + t];
-  if (y < 0 || y >= V1) y = 0;
-  dlogp[((size_t)n * T + t) * V1 + y] = -mask[(size_t)n * ldm + t] / loss_den[1] * grad_out;
-}
-// RewardCriterion (P/misc/criterion.py:117-124), one block
-__global__ void reward_crit_kernel(int N, int L, const float* logp, const int64_t* seq, const float* reward, float* loss_out, float* dlogp) {
-  // One workgroup (the sums are small and their order is part of the result).  Eight elements per thread in flight: with one
-  // element per trip the 40 trips of a 640 x 16 step were 40 memory latencies in a row (40 us between the reward and the backward
-  // pass of the self-critical step).  The per-thread sums still run over i = tid, tid + 256, ... in that order.
-  __shared__ float s_a[256], s_b[256];
-  const int total = N * L;
-  float a = 0.f, b = 0.f;
-  for (int i0 = threadIdx.x; i0 < total; i0 += 256 * 8) {
-    float lp[8], rw[8], m[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int i = i0 + u * 256;
-      const bool in = i < total;
-      const int n = in ? i / L : 0, t = in ? i - n * L : 0;
-      lp[u] = in ? logp[i] : 0.f;
-      rw[u] = in ? reward[i] : 0.f;
-      m[u] = !in ? 0.f : (t == 0 || seq[(size_t)n * L + t - 1] > 0) ? 1.f : 0.f;
-    }
-#pragma unroll
-    for (int u = 0; u < 8; ++u)
-      if (i0 + u * 256 < total) { a += -lp[u] * rw[u] * m[u]; b += m[u]; }
-  }
-  s_a[threadIdx.x] = a; s_b[threadIdx.x] = b;
-  __syncthreads();
-  for (int o = 128; o > 0; o >>= 1) {
-    if ((int)threadIdx.x < o) { s_a[threadIdx.x] += s_a[threadIdx.x + o]; s_b[threadIdx.x] += s_b[threadIdx.x + o]; }
-    __syncthreads();
-  }
-  const float den = s_b[0];
-  if (threadIdx.x == 0) loss_out[0] = s_a[0] / den;
-  if (dlogp)
-    for (int i0 = threadIdx.x; i0 < total; i0 += 256 * 8) {
-      float rw[8], m[8];
-#pragma unroll
-      for (int u = 0; u < 8; ++u) {
-        const int i = i0 + u * 256;
-        const bool in = i < total;
-        const int n = in ? i / L : 0, t = in ? i - n * L : 0;
-        rw[u] = in ? reward[i] : 0.f;
-        m[u] = !in ? 0.f : (t == 0 || seq[(size_t)n * L + t - 1] > 0) ? 1.f : 0.f;
-      }
-#pragma unroll
-      for (int u = 0; u < 8; ++u)
-        if (i0 + u * 256 < total) dlogp[i0 + u * 256] = -rw[u] * m[u] / den;
-    }
-}
-}  // namespace
 
 extern "C" {
 
@@ -263,26 +192,14 @@ int uic_adam_step(float* p, const float* g, float* m, float* v, size_t n, float 
                   float eps, int32_t step, float grad_scale, void* stream) {
   UIC_REQUIRE(p && g && m && v, "adam_step: null pointer");
   UIC_REQUIRE(step >= 1, "adam_step: step=%d must be >= 1", step);
-  UicAdamParams a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-  a.grad_scale = grad_scale;
-  a.max_norm = 0.f; a.sqnorm = nullptr; a.guard = nullptr;
-  return uic_adam_launch(a, (hipStream_t)stream);
+  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, 0.f, nullptr, nullptr), (hipStream_t)stream);
 }
 
 int uic_adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                           float eps, int32_t step, float grad_scale, const int32_t* skip_if_nonzero, void* stream) {
   UIC_REQUIRE(p && g && m && v, "adam_step_guarded: null pointer");
   UIC_REQUIRE(step >= 1, "adam_step_guarded: step=%d must be >= 1", step);
-  UicAdamParams a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-  a.grad_scale = grad_scale;
-  a.max_norm = 0.f; a.sqnorm = nullptr; a.guard = skip_if_nonzero;
-  return uic_adam_launch(a, (hipStream_t)stream);
+  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, 0.f, nullptr, skip_if_nonzero), (hipStream_t)stream);
 }
 
 int uic_grad_sqnorm(const float* g, size_t n, float* scratch, float* out, void* stream) {
@@ -293,13 +210,7 @@ int uic_adam_step_clip(float* p, const float* g, float* m, float* v, size_t n, f
                        float eps, int32_t step, float grad_scale, float max_norm, const float* sqnorm, void* stream) {
   UIC_REQUIRE(p && g && m && v && sqnorm, "adam_step_clip: null pointer");
   UIC_REQUIRE(step >= 1 && max_norm > 0.f, "adam_step_clip: step=%d must be >= 1 and max_norm=%f > 0", step, (double)max_norm);
-  UicAdamParams a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-  a.grad_scale = grad_scale;
-  a.max_norm = max_norm; a.sqnorm = sqnorm; a.guard = nullptr;
-  return uic_adam_launch(a, (hipStream_t)stream);
+  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, nullptr), (hipStream_t)stream);
 }
 
 int uic_adam_step_clip_guarded(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
@@ -307,13 +218,7 @@ int uic_adam_step_clip_guarded(float* p, const float* g, float* m, float* v, siz
                                const int32_t* skip_if_nonzero, void* stream) {
   UIC_REQUIRE(p && g && m && v && sqnorm, "adam_step_clip_guarded: null pointer");
   UIC_REQUIRE(step >= 1 && max_norm > 0.f, "adam_step_clip_guarded: step=%d must be >= 1 and max_norm=%f > 0", step, (double)max_norm);
-  UicAdamParams a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-  a.grad_scale = grad_scale;
-  a.max_norm = max_norm; a.sqnorm = sqnorm; a.guard = skip_if_nonzero;
-  return uic_adam_launch(a, (hipStream_t)stream);
+  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, skip_if_nonzero), (hipStream_t)stream);
 }
 
 int uic_adam_step_ranges(float* p, const float* g, float* m, float* v, int32_t n_ranges, const uint64_t* lo, const uint64_t* hi,
@@ -324,12 +229,7 @@ int uic_adam_step_ranges(float* p, const float* g, float* m, float* v, int32_t n
   UIC_REQUIRE(n_ranges >= 0 && n_ranges <= UIC_ADAM_RANGES, "adam_step_ranges: %d ranges (max %d)", n_ranges, UIC_ADAM_RANGES);
   UIC_REQUIRE(!w_out || w_dtype == UIC_F32 || w_dtype == UIC_BF16, "adam_step_ranges: bad w_dtype %d", w_dtype);
   UIC_REQUIRE((max_norm > 0.f) == (sqnorm != nullptr), "adam_step_ranges: max_norm and sqnorm go together");
-  UicAdamParams a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.n = 0; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-  a.grad_scale = grad_scale;
-  a.max_norm = max_norm; a.sqnorm = sqnorm; a.guard = skip_if_nonzero;
+  const UicAdamParams a = adam_params(p, g, m, v, 0, lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, skip_if_nonzero);
   UicAdamRanges r;
   memset(&r, 0, sizeof(r));
   for (int i = 0; i < n_ranges; ++i) {
@@ -344,32 +244,14 @@ int uic_lm_criterion(int32_t N, int32_t T, int32_t V1, const float* logp, const 
                      const float* mask, int32_t ld_mask, float* loss_out, float* scratch, float* dlogp, float grad_out,
                      void* stream) {
   UIC_REQUIRE(logp && target && mask && loss_out && scratch, "lm_criterion: null pointer");
-  hipStream_t s = (hipStream_t)stream;
-  const int n = N * T;
-  if (n == 0) return UIC_OK;
-  float* row_loss = scratch;
-  float* row_mask = scratch + n;
-  float* fin = scratch + 2 * (size_t)n;   // {loss, den}
-  hipLaunchKernelGGL(lm_crit_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, N, T, V1, logp, target, ld_target, mask, ld_mask, row_loss, row_mask);
-  UIC_LAUNCH_CHECK("lm_crit_rows");
-  hipLaunchKernelGGL(lm_crit_final_kernel, dim3(1), dim3(256), 0, s, row_loss, row_mask, n, fin);
-  UIC_LAUNCH_CHECK("lm_crit_final");
-  UIC_TRY(uic_copy_launch(loss_out, fin, 4, s));
-  if (dlogp) {
-    UIC_TRY(uic_fill_launch(dlogp, 0, (size_t)n * V1 * 4, s));
-    hipLaunchKernelGGL(lm_crit_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, s, N, T, V1, target, ld_target, mask, ld_mask, fin, grad_out, dlogp);
-    UIC_LAUNCH_CHECK("lm_crit_bwd");
-  }
-  return UIC_OK;
+  return uic_lm_crit_launch(N, T, V1, logp, target, ld_target, mask, ld_mask, loss_out, scratch, dlogp, grad_out, (hipStream_t)stream);
 }
 
 int uic_reward_criterion(int32_t N, int32_t L, const float* logp, const int64_t* seq, const float* reward, float* loss_out,
                          float* dlogp, void* stream) {
   UIC_REQUIRE(logp && seq && reward && loss_out, "reward_criterion: null pointer");
   UIC_REQUIRE(N > 0 && L > 0, "reward_criterion: empty input");
-  hipLaunchKernelGGL(reward_crit_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, N, L, logp, seq, reward, loss_out, dlogp);
-  UIC_LAUNCH_CHECK("reward_crit_kernel");
-  return UIC_OK;
+  return uic_reward_crit_launch(N, L, logp, seq, reward, loss_out, dlogp, (hipStream_t)stream);
 }
 
 int uic_xe_criterion(int32_t dtype, int32_t M, int32_t N, int32_t V1, int32_t ldv, const float* logits, void* dlogits,
@@ -457,7 +339,7 @@ int uic_batchnorm_fold_grad(const float* W, const float* gamma, const float* bet
 #undef UIC_BN_SHAPE
 
 // nn.Embedding (+ ReLU + Dropout) forward and its bucketed backward on their own: argument checks here, the launchers of
-// csrc/pointwise.hip do the work.  The alignments are those of the kernels' vector loads: f32 rows are read and stored as float4,
+// csrc/embedding.hip do the work.  The alignments are those of the kernels' vector loads: f32 rows are read and stored as float4,
 // a bf16 table and a bf16 xt as uint2; scratch holds the int4 loads of the scan and the float4 partial rows.
 #define UIC_EMB_DTYPE(dt, who) UIC_REQUIRE((dt) == UIC_F32 || (dt) == UIC_BF16, who ": bad dtype %d", (int)(dt))
 #define UIC_EMB_ALIGNED(p, bytes, who, name) \

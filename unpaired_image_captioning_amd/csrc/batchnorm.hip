@@ -9,6 +9,7 @@
 // use_bn == 2: a second BatchNorm1d(rnn_size) after the Dropout; padded regions stay exactly zero.
 // All reductions are two-stage in a fixed order (deterministic); batch statistics are merged with Chan's formula.
 #include "uic_common.h"
+#include "uic_host.h"
 
 namespace {
 
@@ -278,7 +279,6 @@ inline int chunks_for(int NR, int* rows_per_chunk) {
   *rows_per_chunk = rpc;
   return n;
 }
-inline int gridn(size_t n) { size_t g = (n + NT - 1) / NT; return (int)(g > 65536 ? 65536 : (g ? g : 1)); }
 
 }  // namespace
 
@@ -313,7 +313,7 @@ int uic_bn_stats_running_launch(const float* run_mean, const float* run_var, int
 int uic_bn_apply_launch(int in_dtype, int out_dtype, const void* x, int NR, int R, int C, const int* row_len, const float* stat,
                         const float* gamma, const float* beta, int zero_padded, void* out, hipStream_t s) {
   UIC_REQUIRE(x && stat && out && C % 4 == 0, "bn_apply: bad arguments");
-  const int g = gridn((size_t)NR * (C / 4));
+  const int g = uic_grid_for((size_t)NR * (C / 4), NT);
 #define BN_APPLY(TI, TO) hipLaunchKernelGGL((bn_apply_kernel<TI, TO>), dim3(g), dim3(NT), 0, s, (const TI*)x, (size_t)NR, R, C, row_len, stat, gamma, beta, zero_padded, (TO*)out)
   if (in_dtype == UIC_BF16) { if (out_dtype == UIC_BF16) BN_APPLY(bf16_t, bf16_t); else BN_APPLY(bf16_t, float); }
   else { if (out_dtype == UIC_BF16) BN_APPLY(float, bf16_t); else BN_APPLY(float, float); }
@@ -335,7 +335,7 @@ int uic_bn_bwd_launch(int dtype, float* d, const void* y, int NR, int R, int C, 
   UIC_LAUNCH_CHECK("bn_bwd_part");
   hipLaunchKernelGGL(bn_bwd_final_kernel, dim3((C + 63) / 64), dim3(NT), 0, s, part, nch, C, red, dgamma, dbeta);
   UIC_LAUNCH_CHECK("bn_bwd_final");
-  const int g = gridn((size_t)NR * (C / 4));
+  const int g = uic_grid_for((size_t)NR * (C / 4), NT);
   if (dtype == UIC_BF16)
     hipLaunchKernelGGL(bn_bwd_apply_kernel<bf16_t>, dim3(g), dim3(NT), 0, s, d, (const bf16_t*)y, (size_t)NR, R, C, row_len, stat, gamma, red, training);
   else

@@ -98,7 +98,7 @@ __global__ __launch_bounds__(256) void h2att_cell_bwd_kernel(const UicH2attCellP
 #pragma unroll
       for (int r = 0; r < 4; ++r) red[wave][(16 * i + 4 * lq + r) * FT + 16 * j + l15] = acc[i][j][r];
   __syncthreads();
-  // ---- the cell backward (same formulas as lstm_bwd_kernel, pointwise.hip), d h = GEMM + slab sums in a fixed order
+  // ---- the cell backward (same formulas as lstm_bwd_kernel, lstm_cell.hip), d h = GEMM + slab sums in a fixed order
   float dh[4];
   {
     const int o = (tid >> 3) * FT + 4 * (tid & 7);

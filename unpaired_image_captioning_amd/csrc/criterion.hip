@@ -2,6 +2,8 @@
 // criterion.py:143-150: d logits = (softmax - onehot) * mask / sum(mask)), one workgroup per (t, n) row of logits (gfx950).
 // Five kernels for five row lengths / outputs (uic_xe_launch picks); what they share -- the position of a row, its target and
 // mask, the accuracy counters, the gradient weight, the 4-wide gradient store, the log-prob row -- is written once, below.
+// Behind them the two criteria on materialised log-probs of the single-operator API: LanguageModelCriterion
+// (criterion.py:143-150) and RewardCriterion (criterion.py:117-124).
 #include "uic_common.h"
 #include "../../include/uic_hip.h"
 
@@ -345,7 +347,89 @@ __global__ __launch_bounds__(NT) void logsoftmax_bwd_kernel(T* __restrict__ dlog
   }
 }
 
-// Which kernel takes a launch.  The four bf16 kernels load 16 bytes at a time; everything else -- f32, a row stride that is
+// ------------------------------------------------------------------ the criteria on materialised log-probs
+// LanguageModelCriterion on materialised log-probs (P/misc/criterion.py:143-150)
+__global__ void lm_crit_rows_kernel(int N, int T, int V1, const float* logp, const int64_t* target, int ldt,
+                                    const float* mask, int ldm, float* row_loss, float* row_mask) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * T) return;
+  const int n = i / T, t = i - n * T;
+  long y = target[(size_t)n * ldt + t];
+  if (y < 0 || y >= V1) y = 0;
+  const float m = mask[(size_t)n * ldm + t];
+  row_loss[i] = -logp[((size_t)n * T + t) * V1 + y] * m;
+  row_mask[i] = m;
+}
+__global__ void lm_crit_final_kernel(const float* row_loss, const float* row_mask, int n, float* out) {
+  __shared__ float s_a[256], s_b[256];
+  float a = 0.f, b = 0.f;
+  for (int i = threadIdx.x; i < n; i += 256) { a += row_loss[i]; b += row_mask[i]; }
+  s_a[threadIdx.x] = a; s_b[threadIdx.x] = b;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { s_a[threadIdx.x] += s_a[threadIdx.x + o]; s_b[threadIdx.x] += s_b[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) { out[0] = s_a[0] / s_b[0]; out[1] = s_b[0]; }
+}
+__global__ void lm_crit_bwd_kernel(int N, int T, int V1, const int64_t* target, int ldt, const float* mask, int ldm,
+                                   const float* loss_den, float grad_out, float* dlogp) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= N * T) return;
+  const int n = i / T, t = i - n * T;
+  long y = target[(size_t)n * ldt + t];
+  if (y < 0 || y >= V1) y = 0;
+  dlogp[((size_t)n * T + t) * V1 + y] = -mask[(size_t)n * ldm + t] / loss_den[1] * grad_out;
+}
+// RewardCriterion (P/misc/criterion.py:117-124), one block
+__global__ void reward_crit_kernel(int N, int L, const float* logp, const int64_t* seq, const float* reward, float* loss_out, float* dlogp) {
+  // One workgroup (the sums are small and their order is part of the result).  Eight elements per thread in flight: with one
+  // element per trip the 40 trips of a 640 x 16 step were 40 memory latencies in a row (40 us between the reward and the backward
+  // pass of the self-critical step).  The per-thread sums still run over i = tid, tid + 256, ... in that order.
+  __shared__ float s_a[256], s_b[256];
+  const int total = N * L;
+  float a = 0.f, b = 0.f;
+  for (int i0 = threadIdx.x; i0 < total; i0 += 256 * 8) {
+    float lp[8], rw[8], m[8];
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const int i = i0 + u * 256;
+      const bool in = i < total;
+      const int n = in ? i / L : 0, t = in ? i - n * L : 0;
+      lp[u] = in ? logp[i] : 0.f;
+      rw[u] = in ? reward[i] : 0.f;
+      m[u] = !in ? 0.f : (t == 0 || seq[(size_t)n * L + t - 1] > 0) ? 1.f : 0.f;
+    }
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+      if (i0 + u * 256 < total) { a += -lp[u] * rw[u] * m[u]; b += m[u]; }
+  }
+  s_a[threadIdx.x] = a; s_b[threadIdx.x] = b;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if ((int)threadIdx.x < o) { s_a[threadIdx.x] += s_a[threadIdx.x + o]; s_b[threadIdx.x] += s_b[threadIdx.x + o]; }
+    __syncthreads();
+  }
+  const float den = s_b[0];
+  if (threadIdx.x == 0) loss_out[0] = s_a[0] / den;
+  if (dlogp)
+    for (int i0 = threadIdx.x; i0 < total; i0 += 256 * 8) {
+      float rw[8], m[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int i = i0 + u * 256;
+        const bool in = i < total;
+        const int n = in ? i / L : 0, t = in ? i - n * L : 0;
+        rw[u] = in ? reward[i] : 0.f;
+        m[u] = !in ? 0.f : (t == 0 || seq[(size_t)n * L + t - 1] > 0) ? 1.f : 0.f;
+      }
+#pragma unroll
+      for (int u = 0; u < 8; ++u)
+        if (i0 + u * 256 < total) dlogp[i0 + u * 256] = -rw[u] * m[u] / den;
+    }
+}
+
+// Which kernel takes a launch of uic_xe_launch.  The four bf16 kernels load 16 bytes at a time; everything else -- f32, a row stride that is
 // not a multiple of 4, logits that are not 16-byte aligned -- goes to the generic kernel.
 int xe_choose(const UicXeParams& p) {
   if (!(p.dtype == UIC_BF16 && p.ldv % 4 == 0 && ((uintptr_t)p.logits & 15) == 0)) return UIC_XE_GENERIC;
@@ -401,5 +485,33 @@ int uic_logsoftmax_bwd_launch(int dtype, void* dlogits, int M, int V1, int ldv, 
   if (dtype == UIC_BF16) hipLaunchKernelGGL(logsoftmax_bwd_kernel<bf16_t>, dim3(M), dim3(NT), 0, s, (bf16_t*)dlogits, V1, ldv, N, g, g_step_stride, g_row_stride, logprobs);
   else hipLaunchKernelGGL(logsoftmax_bwd_kernel<float>, dim3(M), dim3(NT), 0, s, (float*)dlogits, V1, ldv, N, g, g_step_stride, g_row_stride, logprobs);
   UIC_LAUNCH_CHECK("logsoftmax_bwd");
+  return UIC_OK;
+}
+
+// scratch: row_loss [N T] | row_mask [N T] | {loss, den}
+int uic_lm_crit_launch(int N, int T, int V1, const float* logp, const int64_t* target, int ld_target, const float* mask, int ld_mask,
+                       float* loss_out, float* scratch, float* dlogp, float grad_out, hipStream_t s) {
+  const int n = N * T;
+  if (n == 0) return UIC_OK;
+  float* row_loss = scratch;
+  float* row_mask = scratch + n;
+  float* fin = scratch + 2 * (size_t)n;   // {loss, den}
+  hipLaunchKernelGGL(lm_crit_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, N, T, V1, logp, target, ld_target, mask, ld_mask, row_loss, row_mask);
+  UIC_LAUNCH_CHECK("lm_crit_rows");
+  hipLaunchKernelGGL(lm_crit_final_kernel, dim3(1), dim3(256), 0, s, row_loss, row_mask, n, fin);
+  UIC_LAUNCH_CHECK("lm_crit_final");
+  UIC_TRY(uic_copy_launch(loss_out, fin, 4, s));
+  if (dlogp) {
+    UIC_TRY(uic_fill_launch(dlogp, 0, (size_t)n * V1 * 4, s));
+    hipLaunchKernelGGL(lm_crit_bwd_kernel, dim3((n + 255) / 256), dim3(256), 0, s, N, T, V1, target, ld_target, mask, ld_mask, fin, grad_out, dlogp);
+    UIC_LAUNCH_CHECK("lm_crit_bwd");
+  }
+  return UIC_OK;
+}
+
+int uic_reward_crit_launch(int N, int L, const float* logp, const int64_t* seq, const float* reward, float* loss_out, float* dlogp,
+                           hipStream_t s) {
+  hipLaunchKernelGGL(reward_crit_kernel, dim3(1), dim3(256), 0, s, N, L, logp, seq, reward, loss_out, dlogp);
+  UIC_LAUNCH_CHECK("reward_crit_kernel");
   return UIC_OK;
 }

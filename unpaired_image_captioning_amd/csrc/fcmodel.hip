@@ -223,7 +223,7 @@ int uic_fc_xe_loss(const uic_fc_dims* d, const uic_topdown_batch* b, int32_t s_r
   hipStream_t s = (hipStream_t)stream;
   const FcLayout L = fc_layout(*d, nullptr, workspace);
   const int N = d->N, V1 = d->V1, V1p = (int)vpad(V1), T = d->S - 1;
-  UIC_TRY(uic_masked_sum_launch(nullptr, b->masks, b->ld_masks, 1, N, T, L.scalars, L.scalars + 1, s));
+  UIC_TRY(uic_masked_sum_launch(b->masks, b->ld_masks, 1, N, T, L.scalars, L.scalars + 1, s));
   const float* inv = inv_den ? inv_den : L.scalars + 1;
   UicXeParams x;
   memset(&x, 0, sizeof(x));
@@ -232,7 +232,7 @@ int uic_fc_xe_loss(const uic_fc_dims* d, const uic_topdown_batch* b, int32_t s_r
   x.mask = b->masks; x.ldmask = b->ld_masks; x.mask_col0 = 1;
   x.inv_den = inv; x.row_loss = L.row_loss; x.write_grad = 1;
   UIC_TRY(uic_xe_launch(x, s));
-  return uic_reduce_sum_launch(L.row_loss, (size_t)(s_run - 1) * N, 0.f, inv, loss_out, s);
+  return uic_reduce_sum_launch(L.row_loss, (size_t)(s_run - 1) * N, inv, loss_out, s);
 }
 
 int uic_fc_backward(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* b, int32_t s_run,
@@ -297,7 +297,7 @@ int uic_fc_backward(const uic_fc_dims* d, const uic_fc_weights* w, const uic_top
     g.C = L.dx_all; g.ldc = E; g.flags = UIC_GEMM_OUT_F32;
     UIC_TRY(uic_gemm_launch(g, s));
   }
-  // (bucketed by word, one owner per table row: bit-reproducible, no floating-point atomics -- csrc/pointwise.hip)
+  // (bucketed by word, one owner per table row: bit-reproducible, no floating-point atomics -- csrc/embedding.hip)
   UIC_TRY(uic_embed_bwd_sorted_launch(dt, L.dx_all + (size_t)N * E, nullptr, b->labels, b->ld_labels, N, s_run - 1, V1, E, 0.f, -1, G->embed_w,
                                       L.embed_scratch, s));
   // img_embed from d x_0

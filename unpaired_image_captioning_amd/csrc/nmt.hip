@@ -369,7 +369,6 @@ __global__ void fill_f32_kernel(float* p, float v, int n) {
   if (i < n) p[i] = v;
 }
 
-inline int gridn(size_t n) { size_t g = (n + NT - 1) / NT; return (int)(g > 65536 ? 65536 : (g ? g : 1)); }
 
 // ---- translator bookkeeping (NMTModel.translateBatch + O/Beam.py); rows are sentence-major: row = b * K + k
 // dst[s, b * K + k] = src[s, b]
@@ -883,7 +882,7 @@ struct Nmt {
         p.row0 = 0; p.Nrows = B;
         UIC_TRY(uic_nmt_enc_fwd_persist_launch(p, s));
         if (l + 1 < NL && drop_p > 0.f) {
-          NMT_T(dropout_apply_kernel, gridn((size_t)S * BH), 0, (const void*)off(L.xl[l + 1], BH, dt), (void*)offw(L.xd[l + 1], BH, dt),
+          NMT_T(dropout_apply_kernel, uic_grid_for((size_t)S * BH, NT), 0, (const void*)off(L.xl[l + 1], BH, dt), (void*)offw(L.xd[l + 1], BH, dt),
                 (size_t)S * BH, drop_p, seed, SITE_NMT_ENC(l));
         }
         continue;
@@ -918,20 +917,20 @@ struct Nmt {
       }
       UIC_TRY(uic_check_hip(hipStreamWaitEvent(s, ss->ev_done, 0), "hipStreamWaitEvent"));
       if (l + 1 < NL && drop_p > 0.f) {  // nn.LSTM's inter-layer dropout (element index over the [S*B, H] slots 1..S)
-        NMT_T(dropout_apply_kernel, gridn((size_t)S * BH), 0, (const void*)off(L.xl[l + 1], BH, dt), (void*)offw(L.xd[l + 1], BH, dt),
+        NMT_T(dropout_apply_kernel, uic_grid_for((size_t)S * BH, NT), 0, (const void*)off(L.xl[l + 1], BH, dt), (void*)offw(L.xd[l + 1], BH, dt),
               (size_t)S * BH, drop_p, seed, SITE_NMT_ENC(l));
       }
     }
     // decoder initial state (_fix_enc_hidden + init_decoder_state, :284-295): slot 0 of the decoder state buffers
     for (int l = 0; l < NL; ++l)
-      NMT_T(enc_final_kernel, gridn(BH), 0, (const void*)L.xl[l + 1], (const float*)L.c_e[l][0], (const float*)L.c_e[l][1],
+      NMT_T(enc_final_kernel, uic_grid_for(BH, NT), 0, (const void*)L.xl[l + 1], (const float*)L.c_e[l][0], (const float*)L.c_e[l][1],
             lengths_dev, B, H, Hd, (void*)L.hd[l], L.cd[l]);
     return UIC_OK;
   }
 
   int decoder_fwd(hipStream_t s) {
     const int H4 = 4 * H;
-    hipLaunchKernelGGL(nmt_prep_kernel, dim3(gridn((size_t)Td * B)), dim3(NT), 0, s, tgt, Td + 1, B, L.target_bt, L.mask_bt, L.tgt_in);
+    hipLaunchKernelGGL(nmt_prep_kernel, dim3(uic_grid_for((size_t)Td * B, NT)), dim3(NT), 0, s, tgt, Td + 1, B, L.target_bt, L.mask_bt, L.tgt_in);
     UIC_LAUNCH_CHECK("nmt_prep_kernel");
     UIC_TRY(uic_embed_fwd_launch(dt, w->dec_lut, Vt, W, L.tgt_in, 1, Td * B, 1, 0.f, 0, 0, 0, 0, L.emb_d, s));
     {  // layer-0 input projection of the embedding part for all steps (the input-feed part stays in the loop)
@@ -1035,7 +1034,7 @@ struct Nmt {
     }
     if (live) { x.M = live_pad; x.row_map = live_rows; x.row_map_limit = Td * B; }   // (rows of logits / d logits / row_loss by list position)
     UIC_TRY(uic_xe_launch(x, s));
-    UIC_TRY(uic_reduce_sum_launch(L.row_loss, live ? (size_t)live_n : (size_t)Td * B, 0.f, nullptr, loss_out, s));
+    UIC_TRY(uic_reduce_sum_launch(L.row_loss, live ? (size_t)live_n : (size_t)Td * B, nullptr, loss_out, s));
     if (stats_out) {
       UIC_TRY(uic_copy_launch(stats_out, L.stats, 8, s));
     }
@@ -1107,7 +1106,7 @@ struct Nmt {
       const bool last = t == Td - 1;
       void* d_pre = offw(L.d_pre_all, (size_t)t * BH, dt);
       float* d_cq = L.d_cq_all + (size_t)t * B * 2 * H;
-      NMT_T(tanh_drop_bwd_kernel, gridn(BH), 0, (const float*)(L.d_out_all + (size_t)t * BH), (const float*)(last ? nullptr : L.dfeed),
+      NMT_T(tanh_drop_bwd_kernel, uic_grid_for(BH, NT), 0, (const float*)(L.d_out_all + (size_t)t * BH), (const float*)(last ? nullptr : L.dfeed),
             2 * H, H, (const void*)off(L.out_pre, (size_t)t * BH, dt), (int)BH, drop_p, seed, SITE_NMT_OUT(t), d_pre);
       {  // d[c ; q] = d_pre W_out
         UicGemmParams g = gemm_base(dt, B, 2 * H);
@@ -1181,13 +1180,13 @@ struct Nmt {
       add_seg(g, L.dg_d[0], H4, L.dec_wT[0], H4, H4);
       g.C = L.demb_d; g.ldc = W; g.flags = UIC_GEMM_OUT_F32;
       UIC_TRY(uic_gemm_launch(g, s));
-      // (bucketed by word, one owner per table row: bit-reproducible, no floating-point atomics -- csrc/pointwise.hip)
+      // (bucketed by word, one owner per table row: bit-reproducible, no floating-point atomics -- csrc/embedding.hip)
       UIC_TRY(uic_embed_bwd_sorted_launch(dt, L.demb_d, nullptr, L.tgt_in, 1, Md, 1, Vt, W, 0.f, 0, G->dec_lut, L.embed_scratch, s));
     }
     // ---- deferred attention gradients: d context (direct share) and d ctxw, then linear_in through ctxw = context W_in:
     // dW_in = context^T d ctxw,  d context += d ctxw W_in^T
     float* d_top = L.d_lay;
-    NMT_T(gattn_bwd_accum_kernel, gridn((size_t)S * BH), 0, (const float*)L.attn_all, (const float*)L.dscore_all, (const float*)L.d_cq_all,
+    NMT_T(gattn_bwd_accum_kernel, uic_grid_for((size_t)S * BH, NT), 0, (const float*)L.attn_all, (const float*)L.dscore_all, (const float*)L.d_cq_all,
           2 * H, (const void*)off(L.hd[NL - 1], BH, dt), Td, S, B, H, d_top, (void*)L.dctxw);
     {
       const UicGemmTnSeg seg{L.dctxw, H, H};
@@ -1282,7 +1281,7 @@ struct Nmt {
       }
       if (l > 0) {
         if (drop_p > 0.f) {
-          hipLaunchKernelGGL(dropout_grad_kernel, dim3(gridn((size_t)Ms * H)), dim3(NT), 0, s, L.dx_e, (size_t)Ms * H, drop_p, seed, SITE_NMT_ENC(l - 1));
+          hipLaunchKernelGGL(dropout_grad_kernel, dim3(uic_grid_for((size_t)Ms * H, NT)), dim3(NT), 0, s, L.dx_e, (size_t)Ms * H, drop_p, seed, SITE_NMT_ENC(l - 1));
           UIC_LAUNCH_CHECK("dropout_grad_kernel");
         }
         UIC_TRY(uic_copy_launch(L.d_lay, L.dx_e, (size_t)Ms * H * 4, s));
@@ -1437,7 +1436,7 @@ int uic_nmt_translate(const uic_nmt_dims* d, const uic_nmt_weights* w, const int
   const size_t Sz = uic_dtype_size(dt), RH = (size_t)R * H;
   const TrLayout T = tr_layout(*d, K, max_steps, workspace);
   // (1) encoder on the replicated batch, WITHOUT lengths: every position of every row is processed (translateBatch :327)
-  hipLaunchKernelGGL(nmt_replicate_src_kernel, dim3(gridn((size_t)S * R)), dim3(NT), 0, s, src, S, B, K, T.src_rep);
+  hipLaunchKernelGGL(nmt_replicate_src_kernel, dim3(uic_grid_for((size_t)S * R, NT)), dim3(NT), 0, s, src, S, B, K, T.src_rep);
   UIC_LAUNCH_CHECK("nmt_replicate_src_kernel");
   uic_nmt_dims d2 = *d;
   d2.B = R; d2.T = 2; d2.drop_p = 0.f;
@@ -1459,7 +1458,7 @@ int uic_nmt_translate(const uic_nmt_dims* d, const uic_nmt_weights* w, const int
     UIC_TRY(uic_copy_launch(T.c[l][0], L.cd[l], RH * 4, s));
   }
   UIC_TRY(uic_fill_launch(T.feed[0], 0, RH * Sz, s));
-  hipLaunchKernelGGL(nmt_beam_init_kernel, dim3(gridn((size_t)R)), dim3(NT), 0, s, B, K, T.tok, T.scores, T.done, T.flags);
+  hipLaunchKernelGGL(nmt_beam_init_kernel, dim3(uic_grid_for((size_t)R, NT)), dim3(NT), 0, s, B, K, T.tok, T.scores, T.done, T.flags);
   UIC_LAUNCH_CHECK("nmt_beam_init_kernel");
   UIC_TRY(uic_fill_launch(T.prev_ks, 0, (size_t)max_steps * R * 4, s));   // (speculative steps of a frozen search gather parent 0)
   const void* ctx = off(L.xl[NL], (size_t)R * H, dt);            // memory bank [S, R, H] (slot 1 onwards)

@@ -560,7 +560,7 @@ __device__ __forceinline__ void nmt_dec_bwd_steps(const UicNmtDecBwdParams& p, C
       for (int h = 0; h < 2; ++h) acc[h] = Mma<T>::run(af[j], wfrag(j, h), acc[h]);
     reduce2(acc, out);
   };
-  // Backward of one LSTM cell's gate math for this wave's element (csrc/pointwise.hip lstm_bwd_kernel): d gates stored (exchanged,
+  // Backward of one LSTM cell's gate math for this wave's element (csrc/lstm_cell.hip lstm_bwd_kernel): d gates stored (exchanged,
   // and read again by the weight-gradient GEMMs), dc carried.  Its operands -- the forward pass's activated gates and cell states --
   // do not depend on anything this launch computes: cell_load requests them at the top of the step, two group barriers before
   // they are used (requested where they are used, each of them is a memory latency on the step's critical path).

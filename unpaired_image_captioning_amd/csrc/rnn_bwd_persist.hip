@@ -150,7 +150,7 @@ __device__ __forceinline__ void bw_load_pw(const Ctx& c, PwOps& o, const void* g
     o.dh0[k] = dh0 ? bld_f32(rd, 4u * q.e[k]) : 0.f;
   }
 }
-// nn.LSTMCell backward for the lane's (row, unit) pairs (same formulas as lstm_bwd_kernel, pointwise.hip): gate
+// nn.LSTMCell backward for the lane's (row, unit) pairs (same formulas as lstm_bwd_kernel, lstm_cell.hip): gate
 // gradients to dg (exchanged: the next GEMM's A operand), d c updated in place
 __device__ __forceinline__ void bw_cell(const Ctx& c, bool safe, const PwOps& o, const float (&dh)[NP], float (&dc)[NP], void* dg) {
   const RowSet q = bw_rows(c);

@@ -1681,10 +1681,10 @@ int uic_topdown_xe_loss(const uic_topdown_dims* d, const uic_topdown_batch* b, i
   Step st;
   st.init(d, &none, nullptr, b, t_run, 0, 0, workspace, nullptr);
   // denominator: sum of masks[:, 1:T+1] over ALL T columns (criterion.py:146-149), also after an early break
-  UIC_TRY(uic_masked_sum_launch(nullptr, b->masks, b->ld_masks, 1, d->N, d->T, st.L.scalars, st.L.scalars + 1, s));
+  UIC_TRY(uic_masked_sum_launch(b->masks, b->ld_masks, 1, d->N, d->T, st.L.scalars, st.L.scalars + 1, s));
   const float* inv = inv_den ? inv_den : st.L.scalars + 1;
   UIC_TRY(st.xe_rows(0, t_run, inv, nullptr, 1, s));
-  UIC_TRY(uic_reduce_sum_launch(st.L.row_loss, (size_t)t_run * d->N, 0.f, inv, loss_out, s));
+  UIC_TRY(uic_reduce_sum_launch(st.L.row_loss, (size_t)t_run * d->N, inv, loss_out, s));
   if (den_out) UIC_TRY(uic_copy_launch(den_out, st.L.scalars, 4, s));
   return UIC_OK;
 }
@@ -1769,7 +1769,7 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   // behind the branch below it would be dispatched beside the persistent recurrence and wait for a CU until that ends.
   // (A resumed step has no prologue after which the main stream waits for the side stream, and the loop's first logit chunk --
   // its criterion reads the denominator -- runs on the main stream: there the denominator is made on the main stream.)
-  if (b->masks) UIC_TRY(uic_masked_sum_launch(nullptr, b->masks, b->ld_masks, 1, d->N, d->T, st.L.scalars, st.L.scalars + 1,
+  if (b->masks) UIC_TRY(uic_masked_sum_launch(b->masks, b->ld_masks, 1, d->N, d->T, st.L.scalars, st.L.scalars + 1,
                                               (training & 4) ? s : s2));
   // (the live list, when the caller left it to the library: on the side stream ahead of its prologue branch, whose event the main
   // stream waits for before the recurrence -- every logit chunk on either stream is ordered behind it)
@@ -1856,7 +1856,7 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   // launches serve the stream's latency better than 56-workgroup ones -- 3.84 vs 3.99 ms per step beside the stand-in exchange)
   const UicWgPlace beside = comm ? UIC_WG_BESIDE_TN128 : UIC_WG_BESIDE;
   UIC_TRY(st.logit_weight_grads(s2, beside));
-  UIC_TRY(uic_reduce_sum_launch(st.L.row_loss, st.compact ? (size_t)st.live_total() : (size_t)t_run * d->N, 0.f, inv, loss_out, s2));
+  UIC_TRY(uic_reduce_sum_launch(st.L.row_loss, st.compact ? (size_t)st.live_total() : (size_t)t_run * d->N, inv, loss_out, s2));
   if (den_out) UIC_TRY(uic_copy_launch(den_out, st.L.scalars, 4, s2));
   UIC_HIP(hipEventRecord(ss->ev_logit, s2));          // gradient group 0 (logit layer) final: its exchange can start now
   UIC_MARK(10, s2);

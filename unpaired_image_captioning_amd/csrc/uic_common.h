@@ -82,6 +82,21 @@ template <> __device__ __forceinline__ uint4 uic_pack<bf16_t>(const float* f) {
                     uic_pack_bf16x2(f[4], f[5]), uic_pack_bf16x2(f[6], f[7]));
 }
 
+// 4 / 8 consecutive elements of an embedding table row (f32 masters or the bf16 operand copy) as floats: the embedding forward
+// (embedding.hip) and the decode step that embeds its own token (sampling.hip)
+__device__ __forceinline__ void uic_table_load4(const float* p, float* f) { const float4 v = *(const float4*)p; f[0] = v.x; f[1] = v.y; f[2] = v.z; f[3] = v.w; }
+__device__ __forceinline__ void uic_table_load4(const bf16_t* p, float* f) {
+  const uint2 v = *(const uint2*)p;
+  f[0] = __uint_as_float(v.x << 16); f[1] = __uint_as_float(v.x & 0xFFFF0000u); f[2] = __uint_as_float(v.y << 16); f[3] = __uint_as_float(v.y & 0xFFFF0000u);
+}
+__device__ __forceinline__ void uic_table_load8(const float* p, float* f) { uic_table_load4(p, f); uic_table_load4(p + 4, f + 4); }
+__device__ __forceinline__ void uic_table_load8(const bf16_t* p, float* f) {
+  const uint4 v = *(const uint4*)p;
+  const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { f[2 * j] = __uint_as_float(w[j] << 16); f[2 * j + 1] = __uint_as_float(w[j] & 0xFFFF0000u); }
+}
+
 // Counter-based dropout: the keep decision of element `idx` at dropout site `site` is a pure
 // function of (seed, site, idx), so forward, backward and the exported test masks agree.
 __device__ __forceinline__ float uic_drop_scale(unsigned seed, unsigned site, unsigned idx, float p, float inv_keep) {
@@ -524,7 +539,7 @@ int uic_nmt_dec_persist_launch(const UicNmtDecParams& p, hipStream_t s);
 bool uic_rnn_bwd_persist_eligible(int dtype, int N, int H, int A, int R);
 int uic_rnn_bwd_persist_launch(const UicRnnBwdParams& p, hipStream_t s);
 
-// ---------------------------------------------------------------- pointwise (pointwise.hip)
+// ---------------------------------------------------------------- general helper kernels (pointwise.hip)
 int uic_cast_f32_launch(int dtype, const float* src, void* dst, size_t n, hipStream_t s);
 int uic_to_f32_launch(int dtype, const void* src, float* dst, size_t n, hipStream_t s);
 #define UIC_CAST_MULTI 6
@@ -553,6 +568,26 @@ int uic_colsum_launch(int src_dtype, const void* src, int rows, int cols, int ld
                       size_t scratch_floats, hipStream_t s);
 // dst[n, c] = sum_t src[t, n, c]
 int uic_sum_steps_launch(int dtype, const void* src, int T, size_t step_elems, void* dst, hipStream_t s);
+// column sums of a small f32 [rows, ncols] matrix into two destinations (columns [0, n0) -> out0, the rest -> out1), one launch
+int uic_colsum_small_launch(const float* part, int rows, int ncols, int n0, float* out0, float* out1, hipStream_t s);
+// dst = (act > 0 ? scale : 0) * grad ; grad f32, act/dst operand dtype
+int uic_relu_mask_bwd_launch(int dtype, const float* grad, const void* act, float scale, void* dst, size_t n, hipStream_t s);
+// seq_per_img > 1 (features given per image, caption rows = image * S + j):
+//   expand_rows: dst[(i*S + j) * row + e] = cast(src[i * row + e])                       (dst dtype: dtype_out)
+//   expand_drop: out[(i*S + j), e] = cast(y[i, e] * dropout keep-scale of element ((i*S + j) * row + e) at `site`)
+//   relu_mask_bwd_fold: dst[i, e] = cast(sum_j (act[(i*S+j), e] > 0 ? grad[(i*S+j), e] * scale : 0))
+int uic_expand_rows_launch(int dtype_out, const float* src, void* dst, int n_img, int S, size_t row, hipStream_t s);
+int uic_expand_drop_launch(int dtype, const float* y, void* out, int n_img, int S, size_t row, float drop_p, unsigned seed,
+                           unsigned site, hipStream_t s);
+int uic_relu_mask_bwd_fold_launch(int dtype, const float* grad, const void* act, float scale, void* dst, int n_img, int S,
+                                  size_t row, hipStream_t s);
+// out_sum[0] = sum of mask[n, col0 + t] over n < N, t < T, out_inv[0] = 1 / that (either may be null); one workgroup
+int uic_masked_sum_launch(const float* mask, int ldmask, int col0, int N, int T, float* out_sum, float* out_inv, hipStream_t s);
+// out[0] = sum_i x[i] (times scale[0], a device scalar, if given); one workgroup
+int uic_reduce_sum_launch(const float* x, size_t n, const float* scale, float* out, hipStream_t s);
+int uic_dropout_mask_launch(float* out, size_t n, float p, unsigned seed, unsigned site, size_t base, hipStream_t s);
+
+// ---------------------------------------------------------------- word embedding (embedding.hip)
 // table in f32 (table_dtype = UIC_F32) or, for bf16 outputs only, in bf16
 int uic_embed_fwd_t_launch(int dtype, const void* table, int table_dtype, int V1, int E, const int64_t* tokens, int ldtok, int N, int T,
                            float drop_p, unsigned seed, unsigned site, size_t idx_base, int relu, void* out, hipStream_t s);
@@ -572,24 +607,6 @@ int uic_embed_bwd_sorted_prepare(const int64_t* tokens, int ldtok, int N, int T,
 int uic_embed_bwd_sorted_gather(int dtype, const float* dxt, const void* xt, const int64_t* tokens, int ldtok, int N, int T,
                                 int V1, int E, float drop_p, long skip_token, float* dtable, int* scratch, hipStream_t s,
                                 int split = 0, int half = 0);
-// column sums of a small f32 [rows, ncols] matrix into two destinations (columns [0, n0) -> out0, the rest -> out1), one launch
-int uic_colsum_small_launch(const float* part, int rows, int ncols, int n0, float* out0, float* out1, hipStream_t s);
-// dst = (act > 0 ? scale : 0) * grad ; grad f32, act/dst operand dtype
-int uic_relu_mask_bwd_launch(int dtype, const float* grad, const void* act, float scale, void* dst, size_t n, hipStream_t s);
-// seq_per_img > 1 (features given per image, caption rows = image * S + j):
-//   expand_rows: dst[(i*S + j) * row + e] = cast(src[i * row + e])                       (dst dtype: dtype_out)
-//   expand_drop: out[(i*S + j), e] = cast(y[i, e] * dropout keep-scale of element ((i*S + j) * row + e) at `site`)
-//   relu_mask_bwd_fold: dst[i, e] = cast(sum_j (act[(i*S+j), e] > 0 ? grad[(i*S+j), e] * scale : 0))
-int uic_expand_rows_launch(int dtype_out, const float* src, void* dst, int n_img, int S, size_t row, hipStream_t s);
-int uic_expand_drop_launch(int dtype, const float* y, void* out, int n_img, int S, size_t row, float drop_p, unsigned seed,
-                           unsigned site, hipStream_t s);
-int uic_relu_mask_bwd_fold_launch(int dtype, const float* grad, const void* act, float scale, void* dst, int n_img, int S,
-                                  size_t row, hipStream_t s);
-
-// scheduled sampling (AttModel.py:130-143): used[n, t] = u_mask(n) < ss_prob ? draw from softmax(logits_prev[n]) : labels[n, t]
-int uic_ss_sample_launch(const float* logits_prev, int N, int V1, int ldv, const int64_t* labels, int ld_labels, int t,
-                         float ss_prob, unsigned seed, int64_t* used, int ld_used, hipStream_t s);
-int uic_copy_tokens_launch(const int64_t* src, int ld_src, int N, int T, int64_t* dst, int ld_dst, hipStream_t s);
 
 // ---------------------------------------------------------------- BatchNorm1d of att_embed (batchnorm.hip)
 size_t uic_bn_scratch_floats(int NR, int C);
@@ -608,6 +625,7 @@ int uic_bn_fold_weight_launch(int dtype, const float* W, const float* gamma, con
 int uic_bn_fold_grad_launch(const float* W, const float* gamma, const float* beta, float* dW, const float* db, int H, int D,
                             float* dgamma, float* dbeta, hipStream_t s);
 
+// ---------------------------------------------------------------- LSTM cell backward (lstm_cell.hip)
 struct UicLstmBwdParams {
   int dtype, M, H;
   const float* dh0; int lddh0;   // up to three dh sources (null = absent)
@@ -625,6 +643,8 @@ struct UicLstmBwdParams {
 };
 // kernel_id (host, optional): which kernel ran (UIC_LSTM_BWD_SCALAR / _VEC4 / _VEC4_SIMPLE, include/uic_hip.h)
 int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kernel_id = nullptr);
+int uic_maxout_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s);   // gates/dgates are [M,5H]; dh = (dh0 + dh1) * dropout
+// ---------------------------------------------------------------- h2att GEMM + cell backward (bptt_fused.hip)
 // d h = d att_h[N, A] h2attT[H, A]^T + the two slab sources, then the nn.LSTMCell backward of UicLstmBwdParams -- the `h2att`
 // input-gradient GEMM and the att_lstm cell backward of a BPTT step in ONE launch (bptt_fused.hip; bf16)
 struct UicH2attCellParams {
@@ -641,10 +661,8 @@ struct UicH2attCellParams {
 };
 bool uic_h2att_cell_bwd_eligible(const UicH2attCellParams& p);
 int uic_h2att_cell_bwd_launch(const UicH2attCellParams& p, hipStream_t s);
-int uic_maxout_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s);   // gates/dgates are [M,5H]; dh = (dh0 + dh1) * dropout
-int uic_sample_fixup_launch(int N, int L, int ld, const int* n_unfinished, int64_t* seq, float* seq_logp, hipStream_t s);
 
-// log-softmax + criterion (criterion.hip)
+// ---------------------------------------------------------------- log-softmax + criterion (criterion.hip)
 struct UicXeParams {
   int dtype, M, V1, ldv;         // logits f32 [M, ldv] in; dlogits [M, ldv] operand dtype out
   const float* logits;
@@ -665,23 +683,30 @@ struct UicXeParams {
 };
 // kernel_id (host, optional): which of the five kernels ran (UIC_XE_GENERIC ... UIC_XE_BIG, include/uic_hip.h)
 int uic_xe_launch(const UicXeParams& p, hipStream_t s, int32_t* kernel_id = nullptr);
-// rows by index: out[m] = src[map[m]] (rows [M, Mpad) of out, and rows whose index is outside [0, src_rows), cleared) /
-// dst[map[m]] = src[m] (indices outside [0, dst_rows) skipped); row_bytes % 16 == 0
+// general log-softmax backward given dense upstream grad g [N,T,V1] (API-compat path):
+// dlogits = g - softmax * sum(g)
+int uic_logsoftmax_bwd_launch(int dtype, void* dlogits, int M, int V1, int ldv, int N, const float* g,
+                              size_t g_step_stride, size_t g_row_stride, const float* logprobs, hipStream_t s);
+// LanguageModelCriterion on materialised log-probs [N, T, V1]: loss_out[0] = sum(-logp[target] mask) / sum(mask); dlogp (optional)
+// is cleared and gets -mask / sum(mask) * grad_out at the targets.  scratch: 2 N T + 2 floats (row losses | row masks | {loss, den})
+int uic_lm_crit_launch(int N, int T, int V1, const float* logp, const int64_t* target, int ld_target, const float* mask, int ld_mask,
+                       float* loss_out, float* scratch, float* dlogp, float grad_out, hipStream_t s);
+// RewardCriterion: loss_out[0] = sum(-logp reward m) / sum(m), m[n, t] = (t == 0 || seq[n, t - 1] > 0); dlogp (optional) its gradient
+int uic_reward_crit_launch(int N, int L, const float* logp, const int64_t* seq, const float* reward, float* loss_out, float* dlogp,
+                           hipStream_t s);
+
+// ---------------------------------------------------------------- live rows (live_rows.hip)
 // the ascending list of the positions t * N + n (p < M) with mask[n * ld + col0 + t] != 0, padded with -1 up to out_len entries
 // inv (optional, [M]): inv[p] = the list index of position p or -1; zero / zero_bytes (optional): a region cleared by the same launch
 // row_len (optional, [N]): row_len[n] = 1 + the last t with mask[n, col0 + t] != 0 (0: none)
 int uic_live_list_launch(const float* mask, int ld, int col0, int N, int M, int* out, int out_len, hipStream_t s, int* inv = nullptr,
                          void* zero = nullptr, size_t zero_bytes = 0, int* row_len = nullptr);
+// rows by index: out[m] = src[map[m]] (rows [M, Mpad) of out, and rows whose index is outside [0, src_rows), cleared) /
+// dst[map[m]] = src[m] (indices outside [0, dst_rows) skipped); row_bytes % 16 == 0
 int uic_gather_rows_launch(const void* src, const int* map, int src_rows, void* out, int M, int Mpad, size_t row_bytes, hipStream_t s);
 int uic_scatter_rows_launch(const void* src, const int* map, void* dst, int dst_rows, int M, size_t row_bytes, hipStream_t s);
-// general log-softmax backward given dense upstream grad g [N,T,V1] (API-compat path):
-// dlogits = g - softmax * sum(g)
-int uic_logsoftmax_bwd_launch(int dtype, void* dlogits, int M, int V1, int ldv, int N, const float* g,
-                              size_t g_step_stride, size_t g_row_stride, const float* logprobs, hipStream_t s);
-int uic_masked_sum_launch(const float* x, const float* mask, int ldmask, int col0, int N, int T, float* out_sum,
-                          float* out_inv, hipStream_t s);
-int uic_reduce_sum_launch(const float* x, size_t n, float scale_by_dev_ptr_or_one, const float* scale, float* out, hipStream_t s);
 
+// ---------------------------------------------------------------- Adam and the gradient norm (adam.hip)
 struct UicAdamParams {
   float* p; const float* g; float* m; float* v; size_t n;
   float lr, beta1, beta2, eps, bc1, bc2, grad_scale;
@@ -699,6 +724,11 @@ constexpr int UIC_ADAM_RANGES = 24;
 struct UicAdamRanges { int count; size_t total; size_t lo[UIC_ADAM_RANGES]; size_t start[UIC_ADAM_RANGES]; };
 int uic_adam_ranges_launch(const UicAdamParams& a, const UicAdamRanges& r, void* w_out, int w_dtype, hipStream_t s);
 
+// ---------------------------------------------------------------- scheduled sampling and the decode step (sampling.hip)
+// scheduled sampling (AttModel.py:130-143): used[n, t] = u_mask(n) < ss_prob ? draw from softmax(logits_prev[n]) : labels[n, t]
+int uic_ss_sample_launch(const float* logits_prev, int N, int V1, int ldv, const int64_t* labels, int ld_labels, int t,
+                         float ss_prob, unsigned seed, int64_t* used, int ld_used, hipStream_t s);
+int uic_copy_tokens_launch(const int64_t* src, int ld_src, int N, int T, int64_t* dst, int ld_dst, hipStream_t s);
 constexpr int UIC_NUNF_STRIPES = 64;
 struct UicSampleParams {
   int dtype, N, V1, ldv, t, L;
@@ -721,6 +751,8 @@ struct UicSampleParams {
   const void* embed_table; int embed_table_dtype; int embed_V1, embed_E; float embed_drop_p; unsigned embed_site; size_t embed_idx_base; void* xt_out;
 };
 int uic_sample_step_launch(const UicSampleParams& p, hipStream_t s);
+// FCModel_NMT._sample: clears the column at which every row had finished and everything after it
+int uic_sample_fixup_launch(int N, int L, int ld, const int* n_unfinished, int64_t* seq, float* seq_logp, hipStream_t s);
 // ---- beam search bookkeeping (beam.hip): rows = (image, beam)
 #define UIC_BEAM_MAX 16
 struct UicBeamParams {
@@ -749,4 +781,3 @@ struct UicEnsembleParams {
   float* out; int ld_out;                                       // [N, ld_out]; columns [V1, ld_out) are not written
 };
 int uic_ensemble_logmean_launch(const UicEnsembleParams& p, hipStream_t s);
-int uic_dropout_mask_launch(float* out, size_t n, float p, unsigned seed, unsigned site, size_t base, hipStream_t s);

@@ -1,9 +1,23 @@
-// Host-side helpers shared by the model-level sequencers (topdown.hip, fcmodel.hip).
+// Host-side helpers shared by the launchers and the model-level sequencers (topdown.hip, fcmodel.hip).
 #pragma once
 #include "uic_common.h"
 #include <string.h>
 
+// one launch per operand dtype
+#define UIC_DISPATCH_T(dtype, CALL_BF16, CALL_F32) \
+  do {                                             \
+    if ((dtype) == UIC_BF16) { CALL_BF16; } else { CALL_F32; } \
+  } while (0)
+
 namespace {
+
+// workgroups of a grid-stride kernel: n elements, per_block of them per workgroup and trip
+inline int uic_grid_for(size_t n, int per_block) {
+  size_t g = (n + per_block - 1) / per_block;
+  if (g > 65536) g = 65536;   // grid-stride beyond that
+  if (g == 0) g = 1;
+  return (int)g;
+}
 
 // bump allocator over a caller-provided arena (base == nullptr: size query)
 struct Bump {
