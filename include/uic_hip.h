@@ -678,11 +678,59 @@ int uic_adam_step_ranges(float* p, const float* g, float* m, float* v, int32_t n
                          float lr, float beta1, float beta2, float eps, int32_t step, float grad_scale, float max_norm,
                          const float* sqnorm, const int32_t* skip_if_nonzero, void* w_out, int32_t w_dtype, void* stream);
 
+/* One step of any --i2t_optim / --nmt_optim method on one flat f32 arena: the torch.optim classes as create_optimizer builds them
+ * (P/misc/optimizer.py:59-74) and Optim.step runs them (:89-100).  With g' = grad_scale * clip * g [+ weight_decay * p] (torch's
+ * coupled L2 term, added AFTER the scale and the clip coefficient, never scaled by them; with it g' is formed in double and
+ * rounded once; weight_decay = 0 adds nothing and leaves the bits of before):
+ *   UIC_OPTIM_ADAM     Adam(lr, (alpha, beta), eps)            s0 = exp_avg, s1 = exp_avg_sq; the update of uic_adam_step
+ *   UIC_OPTIM_SGD      SGD(lr)                                 p -= lr g'
+ *   UIC_OPTIM_SGDM     SGD(lr, momentum=alpha)                 s0 = momentum_buffer: buf = alpha buf + g'; p -= lr buf
+ *   UIC_OPTIM_SGDMOM   SGD(lr, momentum=alpha, nesterov=True)  buf = alpha buf + g'; p -= lr (g' + alpha buf)
+ *   UIC_OPTIM_RMSPROP  RMSprop(lr, alpha, eps)                 s0 = square_avg: sq = alpha sq + (1 - alpha) g'^2; p -= lr g' / (sqrt(sq) + eps)
+ *   UIC_OPTIM_ADAGRAD  Adagrad(lr), lr_decay 0                 s0 = sum: sum += g'^2; p -= lr g' / (sqrt(sum) + eps); the reference
+ *                                                              leaves eps at torch's 1e-10 -- the caller passes it
+ * State arrays start at zero (a zero momentum_buffer gives buf = g' on the first step, as torch's copy does).  `step` is 1-based
+ * and enters Adam's bias corrections only.  max_norm / sqnorm (both or neither): the clip of uic_adam_step_clip.  With
+ * weight_decay != 0 sqnorm points at TWO floats whose sum is the squared norm (uic_grad_sqnorm_f64 leaves them; {norm, 0} is
+ * valid) and the coefficient is formed in double: RMSprop and Adagrad divide by the size of what clip * g and weight_decay * p
+ * leave of each other, and one float's last bit would show there.  With weight_decay = 0 it is one float, as ever;
+ * skip_if_nonzero: the guard of uic_adam_step_guarded. */
+#define UIC_OPTIM_ADAM 0
+#define UIC_OPTIM_SGD 1
+#define UIC_OPTIM_SGDM 2
+#define UIC_OPTIM_SGDMOM 3
+#define UIC_OPTIM_RMSPROP 4
+#define UIC_OPTIM_ADAGRAD 5
+#define UIC_OPTIM_METHODS 6
+typedef struct uic_optim_config {
+  int32_t method;
+  float lr, alpha, beta, eps, weight_decay;
+  int32_t step;
+  float grad_scale, max_norm;
+  const float* sqnorm;
+  const int32_t* skip_if_nonzero;
+} uic_optim_config;
+/* How many of s0 / s1 the method reads and writes (0, 1 or 2; -1: no such method) -- what a caller allocates: SGD's arena has
+ * no optimizer state at all (torch.optim.SGD keeps none either, P/misc/optimizer.py:65). */
+int uic_optim_states(int32_t method);
+/* The step over the whole arena, one launch (Optim.step's optimizer.step(), P/misc/optimizer.py:93,100).  State pointers the
+ * method does not use are ignored and may be NULL. */
+int uic_optim_step(const uic_optim_config* cfg, float* p, const float* g, float* s0, float* s1, size_t n, void* stream);
+/* The step on index ranges of the arena with the optional operand-dtype copy, as uic_adam_step_ranges (the sharded exchange's
+ * optimizer launch, which replaces DataParallel's replicated optimizer.step(), P/trainer.py:74): element for element the
+ * arithmetic of uic_optim_step. */
+int uic_optim_step_ranges(const uic_optim_config* cfg, float* p, const float* g, float* s0, float* s1, int32_t n_ranges,
+                          const uint64_t* lo, const uint64_t* hi, void* w_out, int32_t w_dtype, void* stream);
+
 /* torch.nn.utils.clip_grad_norm + Adam as Optim.step applies them to the NMT model (P/misc/optimizer.py:93-100,
  * --nmt_max_grad_norm 5): uic_grad_sqnorm leaves sum(g^2) of the flat gradient arena in out[0] (deterministic
  * two-stage sum; scratch >= 1024 floats); uic_adam_step_clip scales the gradient by grad_scale and, if
  * max_norm / (|grad_scale| * sqrt(sqnorm[0]) + 1e-6) < 1, by that coefficient too, read on the device. */
 int uic_grad_sqnorm(const float* g, size_t n, float* scratch, float* out, void* stream);
+/* The same sum accumulated in double and left as a PAIR of floats, out[0] + out[1] (the rounded sum and what the rounding
+ * dropped; scratch >= 1024 floats, 8-byte aligned): the norm for the clip of a step WITH weight decay, see uic_optim_config.
+ * uic_grad_sqnorm stays what Adam's clip has always read. */
+int uic_grad_sqnorm_f64(const float* g, size_t n, float* scratch, float* out, void* stream);
 int uic_adam_step_clip(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                        float eps, int32_t step, float grad_scale, float max_norm, const float* sqnorm, void* stream);
 /* ... skipped on the device when skip_if_nonzero[0] has any bit set (as uic_adam_step_guarded: the pivot NMT step's persistent

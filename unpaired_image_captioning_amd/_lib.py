@@ -206,6 +206,16 @@ class Gathered(C.Structure):
     _fields_ = [(f, C.c_void_p) for f, _, _ in GATHERED_FIELDS] + [("logit_h_w", C.c_void_p * (MAX_LOGIT_LAYERS - 1)), ("ready", C.c_void_p * 4)]
 
 
+# UIC_OPTIM_*: the --i2t_optim / --nmt_optim names (P/opts.py) -> uic_optim_config.method
+OPTIM_METHODS = {"adam": 0, "sgd": 1, "sgdm": 2, "sgdmom": 3, "rmsprop": 4, "adagrad": 5}
+
+
+class OptimConfig(C.Structure):
+    """uic_optim_config"""
+    _fields_ = [("method", C.c_int32)] + [(n, C.c_float) for n in ("lr", "alpha", "beta", "eps", "weight_decay")] + \
+        [("step", C.c_int32), ("grad_scale", C.c_float), ("max_norm", C.c_float), ("sqnorm", C.c_void_p), ("skip_if_nonzero", C.c_void_p)]
+
+
 class Batch(C.Structure):
     _fields_ = [("fc_feats", C.c_void_p), ("att_feats", C.c_void_p), ("att_masks", C.c_void_p),
                 ("labels", C.c_void_p), ("ld_labels", C.c_int32),
@@ -331,9 +341,14 @@ _SIGS = {
     "uic_attention_fwd": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 9),
     "uic_attention_bwd_step": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 9),
     "uic_attention_bwd_accum": (C.c_int, [C.c_int32] * 6 + [C.c_void_p] * 10),
+    "uic_optim_states": (C.c_int, [C.c_int32]),
+    "uic_optim_step": (C.c_int, [C.POINTER(OptimConfig)] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
+    "uic_optim_step_ranges": (C.c_int, [C.POINTER(OptimConfig)] + [C.c_void_p] * 4 + [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),
+                                                                                   C.c_void_p, C.c_int32, C.c_void_p]),
     "uic_adam_step": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int32, C.c_float, C.c_void_p]),
     "uic_adam_step_guarded": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int32, C.c_float, C.c_void_p, C.c_void_p]),
     "uic_grad_sqnorm": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uic_grad_sqnorm_f64": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "uic_adam_step_clip": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int32, C.c_float, C.c_float,
                                                                                       C.c_void_p, C.c_void_p]),
     "uic_adam_step_clip_guarded": (C.c_int, [C.c_void_p] * 4 + [C.c_size_t] + [C.c_float] * 4 + [C.c_int32, C.c_float, C.c_float,

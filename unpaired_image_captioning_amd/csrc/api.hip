@@ -21,16 +21,60 @@ int uic_check_hip(hipError_t e, const char* what) {
   return (int)e > 0 ? (int)e : 1;
 }
 
-// UicAdamParams of one optimizer step: the bias corrections 1 - beta^step in double, as torch.optim.Adam computes them
-static UicAdamParams adam_params(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2, float eps,
-                                 int32_t step, float grad_scale, float max_norm, const float* sqnorm, const int32_t* guard) {
-  UicAdamParams a;
-  a.p = p; a.g = g; a.m = m; a.v = v; a.n = n; a.lr = lr; a.beta1 = beta1; a.beta2 = beta2; a.eps = eps;
-  a.bc1 = (float)(1.0 - pow((double)beta1, (double)step));
-  a.bc2 = (float)(1.0 - pow((double)beta2, (double)step));
-  a.grad_scale = grad_scale;
-  a.max_norm = max_norm; a.sqnorm = sqnorm; a.guard = guard;
-  return a;
+// UicOptimParams of one optimizer step; Adam's bias corrections 1 - beta^step in double, as torch.optim.Adam computes them.
+// `what` names the C entry in the error text.  A method's unused state pointers are dropped here, so no kernel can see them.
+static int optim_params(const char* what, const uic_optim_config* c, float* p, const float* g, float* s0, float* s1, size_t n,
+                        UicOptimParams* out) {
+  UIC_REQUIRE(c, "%s: null config", what);
+  const int states = uic_optim_state_count(c->method);
+  UIC_REQUIRE(states >= 0, "%s: unknown method %d", what, c->method);
+  UIC_REQUIRE(p && g && (states < 1 || s0) && (states < 2 || s1), "%s: null pointer", what);
+  UIC_REQUIRE(c->step >= 1, "%s: step=%d must be >= 1", what, c->step);
+  UIC_REQUIRE((c->max_norm > 0.f) == (c->sqnorm != nullptr), "%s: max_norm and sqnorm go together", what);
+  UIC_REQUIRE(c->weight_decay >= 0.f, "%s: weight_decay=%f must be >= 0", what, (double)c->weight_decay);
+  UicOptimParams a;
+  a.method = c->method;
+  a.p = p; a.g = g; a.s0 = states >= 1 ? s0 : nullptr; a.s1 = states >= 2 ? s1 : nullptr; a.n = n;
+  a.lr = c->lr; a.alpha = c->alpha; a.beta = c->beta; a.eps = c->eps; a.weight_decay = c->weight_decay;
+  a.bc1 = a.bc2 = 1.f;
+  if (c->method == UIC_OPTIM_ADAM) {
+    a.bc1 = (float)(1.0 - pow((double)c->alpha, (double)c->step));
+    a.bc2 = (float)(1.0 - pow((double)c->beta, (double)c->step));
+  }
+  a.grad_scale = c->grad_scale;
+  a.max_norm = c->max_norm; a.sqnorm = c->sqnorm; a.guard = c->skip_if_nonzero;
+  *out = a;
+  return UIC_OK;
+}
+static int optim_step(const char* what, const uic_optim_config* c, float* p, const float* g, float* s0, float* s1, size_t n, void* stream) {
+  UicOptimParams a;
+  const int rc = optim_params(what, c, p, g, s0, s1, n, &a);
+  return rc ? rc : uic_optim_launch(a, (hipStream_t)stream);
+}
+static int optim_step_ranges(const char* what, const uic_optim_config* c, float* p, const float* g, float* s0, float* s1, int32_t n_ranges,
+                             const uint64_t* lo, const uint64_t* hi, void* w_out, int32_t w_dtype, void* stream) {
+  UicOptimParams a;
+  const int rc = optim_params(what, c, p, g, s0, s1, 0, &a);
+  if (rc) return rc;
+  UIC_REQUIRE(n_ranges == 0 || (lo && hi), "%s: null pointer", what);
+  UIC_REQUIRE(n_ranges >= 0 && n_ranges <= UIC_OPTIM_RANGES, "%s: %d ranges (max %d)", what, n_ranges, UIC_OPTIM_RANGES);
+  UIC_REQUIRE(!w_out || w_dtype == UIC_F32 || w_dtype == UIC_BF16, "%s: bad w_dtype %d", what, w_dtype);
+  UicOptimRanges r;
+  memset(&r, 0, sizeof(r));
+  for (int i = 0; i < n_ranges; ++i) {
+    UIC_REQUIRE(hi[i] >= lo[i], "%s: range %d is [%llu, %llu)", what, i, (unsigned long long)lo[i], (unsigned long long)hi[i]);
+    if (hi[i] == lo[i]) continue;
+    r.lo[r.count] = (size_t)lo[i]; r.start[r.count] = r.total; r.total += (size_t)(hi[i] - lo[i]); ++r.count;
+  }
+  return uic_optim_ranges_launch(a, r, w_out, w_dtype, (hipStream_t)stream);
+}
+// the uic_adam_* entries' arguments as a config (no weight decay: their bits are those of before uic_optim_step existed)
+static uic_optim_config adam_config(float lr, float beta1, float beta2, float eps, int32_t step, float grad_scale, float max_norm,
+                                    const float* sqnorm, const int32_t* guard) {
+  uic_optim_config c;
+  c.method = UIC_OPTIM_ADAM; c.lr = lr; c.alpha = beta1; c.beta = beta2; c.eps = eps; c.weight_decay = 0.f; c.step = step;
+  c.grad_scale = grad_scale; c.max_norm = max_norm; c.sqnorm = sqnorm; c.skip_if_nonzero = guard;
+  return c;
 }
 
 extern "C" {
@@ -188,56 +232,57 @@ int uic_attention_bwd_accum(int32_t dtype, int32_t N, int32_t R, int32_t A, int3
   return uic_attention_bwd_accum_launch(a, (hipStream_t)stream);
 }
 
+int uic_optim_states(int32_t method) { return uic_optim_state_count(method); }
+
+int uic_optim_step(const uic_optim_config* cfg, float* p, const float* g, float* s0, float* s1, size_t n, void* stream) {
+  return optim_step("optim_step", cfg, p, g, s0, s1, n, stream);
+}
+
+int uic_optim_step_ranges(const uic_optim_config* cfg, float* p, const float* g, float* s0, float* s1, int32_t n_ranges,
+                          const uint64_t* lo, const uint64_t* hi, void* w_out, int32_t w_dtype, void* stream) {
+  return optim_step_ranges("optim_step_ranges", cfg, p, g, s0, s1, n_ranges, lo, hi, w_out, w_dtype, stream);
+}
+
 int uic_adam_step(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                   float eps, int32_t step, float grad_scale, void* stream) {
-  UIC_REQUIRE(p && g && m && v, "adam_step: null pointer");
-  UIC_REQUIRE(step >= 1, "adam_step: step=%d must be >= 1", step);
-  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, 0.f, nullptr, nullptr), (hipStream_t)stream);
+  const uic_optim_config c = adam_config(lr, beta1, beta2, eps, step, grad_scale, 0.f, nullptr, nullptr);
+  return optim_step("adam_step", &c, p, g, m, v, n, stream);
 }
 
 int uic_adam_step_guarded(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                           float eps, int32_t step, float grad_scale, const int32_t* skip_if_nonzero, void* stream) {
-  UIC_REQUIRE(p && g && m && v, "adam_step_guarded: null pointer");
-  UIC_REQUIRE(step >= 1, "adam_step_guarded: step=%d must be >= 1", step);
-  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, 0.f, nullptr, skip_if_nonzero), (hipStream_t)stream);
+  const uic_optim_config c = adam_config(lr, beta1, beta2, eps, step, grad_scale, 0.f, nullptr, skip_if_nonzero);
+  return optim_step("adam_step_guarded", &c, p, g, m, v, n, stream);
 }
 
 int uic_grad_sqnorm(const float* g, size_t n, float* scratch, float* out, void* stream) {
   return uic_sqnorm_launch(g, n, scratch, out, (hipStream_t)stream);
 }
 
+int uic_grad_sqnorm_f64(const float* g, size_t n, float* scratch, float* out, void* stream) {
+  return uic_sqnorm_f64_launch(g, n, scratch, out, (hipStream_t)stream);
+}
+
 int uic_adam_step_clip(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                        float eps, int32_t step, float grad_scale, float max_norm, const float* sqnorm, void* stream) {
-  UIC_REQUIRE(p && g && m && v && sqnorm, "adam_step_clip: null pointer");
-  UIC_REQUIRE(step >= 1 && max_norm > 0.f, "adam_step_clip: step=%d must be >= 1 and max_norm=%f > 0", step, (double)max_norm);
-  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, nullptr), (hipStream_t)stream);
+  UIC_REQUIRE(sqnorm && max_norm > 0.f, "adam_step_clip: sqnorm must be given and max_norm=%f > 0", (double)max_norm);
+  const uic_optim_config c = adam_config(lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, nullptr);
+  return optim_step("adam_step_clip", &c, p, g, m, v, n, stream);
 }
 
 int uic_adam_step_clip_guarded(float* p, const float* g, float* m, float* v, size_t n, float lr, float beta1, float beta2,
                                float eps, int32_t step, float grad_scale, float max_norm, const float* sqnorm,
                                const int32_t* skip_if_nonzero, void* stream) {
-  UIC_REQUIRE(p && g && m && v && sqnorm, "adam_step_clip_guarded: null pointer");
-  UIC_REQUIRE(step >= 1 && max_norm > 0.f, "adam_step_clip_guarded: step=%d must be >= 1 and max_norm=%f > 0", step, (double)max_norm);
-  return uic_adam_launch(adam_params(p, g, m, v, n, lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, skip_if_nonzero), (hipStream_t)stream);
+  UIC_REQUIRE(sqnorm && max_norm > 0.f, "adam_step_clip_guarded: sqnorm must be given and max_norm=%f > 0", (double)max_norm);
+  const uic_optim_config c = adam_config(lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, skip_if_nonzero);
+  return optim_step("adam_step_clip_guarded", &c, p, g, m, v, n, stream);
 }
 
 int uic_adam_step_ranges(float* p, const float* g, float* m, float* v, int32_t n_ranges, const uint64_t* lo, const uint64_t* hi,
                          float lr, float beta1, float beta2, float eps, int32_t step, float grad_scale, float max_norm,
                          const float* sqnorm, const int32_t* skip_if_nonzero, void* w_out, int32_t w_dtype, void* stream) {
-  UIC_REQUIRE(p && g && m && v && (n_ranges == 0 || (lo && hi)), "adam_step_ranges: null pointer");
-  UIC_REQUIRE(step >= 1, "adam_step_ranges: step=%d must be >= 1", step);
-  UIC_REQUIRE(n_ranges >= 0 && n_ranges <= UIC_ADAM_RANGES, "adam_step_ranges: %d ranges (max %d)", n_ranges, UIC_ADAM_RANGES);
-  UIC_REQUIRE(!w_out || w_dtype == UIC_F32 || w_dtype == UIC_BF16, "adam_step_ranges: bad w_dtype %d", w_dtype);
-  UIC_REQUIRE((max_norm > 0.f) == (sqnorm != nullptr), "adam_step_ranges: max_norm and sqnorm go together");
-  const UicAdamParams a = adam_params(p, g, m, v, 0, lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, skip_if_nonzero);
-  UicAdamRanges r;
-  memset(&r, 0, sizeof(r));
-  for (int i = 0; i < n_ranges; ++i) {
-    UIC_REQUIRE(hi[i] >= lo[i], "adam_step_ranges: range %d is [%llu, %llu)", i, (unsigned long long)lo[i], (unsigned long long)hi[i]);
-    if (hi[i] == lo[i]) continue;
-    r.lo[r.count] = (size_t)lo[i]; r.start[r.count] = r.total; r.total += (size_t)(hi[i] - lo[i]); ++r.count;
-  }
-  return uic_adam_ranges_launch(a, r, w_out, w_dtype, (hipStream_t)stream);
+  const uic_optim_config c = adam_config(lr, beta1, beta2, eps, step, grad_scale, max_norm, sqnorm, skip_if_nonzero);
+  return optim_step_ranges("adam_step_ranges", &c, p, g, m, v, n_ranges, lo, hi, w_out, w_dtype, stream);
 }
 
 int uic_lm_criterion(int32_t N, int32_t T, int32_t V1, const float* logp, const int64_t* target, int32_t ld_target,

@@ -706,23 +706,31 @@ int uic_live_list_launch(const float* mask, int ld, int col0, int N, int M, int*
 int uic_gather_rows_launch(const void* src, const int* map, int src_rows, void* out, int M, int Mpad, size_t row_bytes, hipStream_t s);
 int uic_scatter_rows_launch(const void* src, const int* map, void* dst, int dst_rows, int M, size_t row_bytes, hipStream_t s);
 
-// ---------------------------------------------------------------- Adam and the gradient norm (adam.hip)
-struct UicAdamParams {
-  float* p; const float* g; float* m; float* v; size_t n;
-  float lr, beta1, beta2, eps, bc1, bc2, grad_scale;
+// ---------------------------------------------------------------- the optimizer step and the gradient norm (adam.hip)
+// One step of method `method` (UIC_OPTIM_*, include/uic_hip.h) on the arena.  s0 / s1: the method's state arrays (Adam: exp_avg,
+// exp_avg_sq; sgdm / sgdmom: momentum_buffer; rmsprop: square_avg; adagrad: sum; the rest unused, may be null).  alpha / beta: Adam's
+// betas; alpha alone is the momentum or RMSprop's smoothing constant.  bc1 / bc2: Adam's bias corrections, unused elsewhere.
+struct UicOptimParams {
+  int method;
+  float* p; const float* g; float* s0; float* s1; size_t n;
+  float lr, alpha, beta, eps, weight_decay, bc1, bc2, grad_scale;
   // clip_grad_norm (P/misc/optimizer.py:99): if sqnorm != null, gradients are additionally scaled by
   // min(1, max_norm / (grad_scale * sqrt(sqnorm[0]) + 1e-6)), read on the device (no host sync)
+  // (weight_decay != 0: the squared norm is the float PAIR sqnorm[0] + sqnorm[1], see uic_sqnorm_f64_launch)
   float max_norm; const float* sqnorm;
-  // uic_adam_step_guarded: if guard != null and guard[0] != 0 (any bit set: an int32 status word or a float sum of them), the
-  // launch changes nothing -- parameters and moments stay those of before the step
+  // if guard != null and guard[0] != 0 (any bit set: an int32 status word or a float sum of them), the launch changes nothing --
+  // parameters and state stay those of before the step
   const int32_t* guard;
 };
 // out[0] = sum_i g[i]^2, deterministic two-stage reduction; scratch >= 1024 floats
 int uic_sqnorm_launch(const float* g, size_t n, float* scratch, float* out, hipStream_t s);
-int uic_adam_launch(const UicAdamParams& a, hipStream_t s);
-constexpr int UIC_ADAM_RANGES = 24;
-struct UicAdamRanges { int count; size_t total; size_t lo[UIC_ADAM_RANGES]; size_t start[UIC_ADAM_RANGES]; };
-int uic_adam_ranges_launch(const UicAdamParams& a, const UicAdamRanges& r, void* w_out, int w_dtype, hipStream_t s);
+// the same sum accumulated in double, as the float pair out[0] + out[1]; scratch >= 1024 floats, 8-byte aligned
+int uic_sqnorm_f64_launch(const float* g, size_t n, float* scratch, float* out, hipStream_t s);
+int uic_optim_state_count(int method);          // 0, 1 or 2; -1: no such method
+int uic_optim_launch(const UicOptimParams& a, hipStream_t s);
+constexpr int UIC_OPTIM_RANGES = 24;
+struct UicOptimRanges { int count; size_t total; size_t lo[UIC_OPTIM_RANGES]; size_t start[UIC_OPTIM_RANGES]; };
+int uic_optim_ranges_launch(const UicOptimParams& a, const UicOptimRanges& r, void* w_out, int w_dtype, hipStream_t s);
 
 // ---------------------------------------------------------------- scheduled sampling and the decode step (sampling.hip)
 // scheduled sampling (AttModel.py:130-143): used[n, t] = u_mask(n) < ss_prob ? draw from softmax(logits_prev[n]) : labels[n, t]

@@ -1,8 +1,8 @@
 """`Optim` with the reference's surface (P/misc/optimizer.py:9-131): set_parameters / step / zero_grad /
 update_LearningRate / update_ScheduledSampling_prob, for the captioner ('i2t') and the pivot NMT model ('nmt').
 
-MI355X-first: each model's parameters, gradients and Adam moments live in ONE flat f32 arena (`FlatArena`), so the
-optimizer step is one kernel launch (`uic_adam_step[_clip]`) instead of ~40 per-tensor launches, gradient clipping
+MI355X-first: each model's parameters, gradients and optimizer state live in ONE flat f32 arena (`FlatArena`), so the
+optimizer step is one kernel launch (`uic_optim_step`) instead of ~40 per-tensor launches, gradient clipping
 reads the squared norm from the device (no host sync), and data parallelism is one RCCL all-reduce of the gradient
 arena.  `p.grad` of every parameter is a view of the arena, so `loss.backward()` accumulates straight into it.
 
@@ -13,7 +13,19 @@ Reference behaviour kept on purpose:
     max_norm / (norm + 1e-6) applied only when < 1 (torch.nn.utils.clip_grad_norm);
   * 'noam' sets lr = nmt_lr * rnn_size^-0.5 * min(step^-0.5, step * warmup^-1.5) from the SHARED step counter (:95-98);
   * update_LearningRate('nmt') is a single-shot decay (lr * rate, not rate^k, :125-131).
-Only Adam is on the hot path; other methods raise NotImplementedError.
+
+Every --i2t_optim / --nmt_optim method runs on that path (csrc/adam.hip), with the hyper-parameters the reference's
+create_optimizer hands torch.optim positionally (:59-74):
+  rmsprop  RMSprop(lr, optim_alpha, optim_epsilon)        state square_avg
+  adagrad  Adagrad(lr), eps stays torch's 1e-10           state sum
+  sgd      SGD(lr)                                        no state: the arena allocates none
+  sgdm     SGD(lr, momentum=optim_alpha)                  state momentum_buffer
+  sgdmom   SGD(lr, momentum=optim_alpha, nesterov=True)   state momentum_buffer
+  adam     Adam(lr, (optim_alpha, optim_beta), optim_epsilon)   state exp_avg, exp_avg_sq
+--*_momentum is read by nothing, as in the reference; any other name raises RuntimeError("Invalid optim method: ...") from
+set_parameters.  --*_weight_decay is torch's coupled L2 term for every method: g <- grad_scale * clip * g + wd * p, added on
+the device after the scale and the clip coefficient (clip_grad_norm, then optimizer.step(), :99-100).  The one launch, the
+clip read on the device, the guard word, the ranges form of the sharded exchange and the optimizer files hold for each.
 """
 import torch
 
@@ -22,7 +34,10 @@ from .._lib import check, ptr, stream
 
 
 class FlatArena(object):
-    """All parameters of a module re-homed into one flat f32 tensor (plus same-layout grad / Adam arenas).
+    """All parameters of a module re-homed into one flat f32 tensor (plus same-layout grad / optimizer-state arenas).
+
+    method: the --i2t_optim / --nmt_optim name (METHODS); it fixes which state arenas exist -- Adam's `exp_avg` / `exp_avg_sq`,
+    `momentum_buffer`, `square_avg`, `sum`, or none for sgd -- and which update adam() / adam_owned() / sharded_step() launch.
 
     pieces (data parallel, world > 1): lists of parameter names -- the SHARDED gradient pieces, in the order in which the backward
     pass makes them final.  Each piece is padded to a multiple of 64 * world elements and split evenly over the ranks: rank r owns
@@ -35,8 +50,17 @@ class FlatArena(object):
     gather_masters()); None / float32: the all-gather runs on the f32 masters in place."""
 
     SCALAR_SLOTS = 64
+    # method (--i2t_optim / --nmt_optim, P/misc/optimizer.py:59-74) -> the torch.optim class the reference builds and the names
+    # of its per-parameter state tensors, which are also the names of this arena's state arenas
+    METHODS = {'adam': (torch.optim.Adam, ('exp_avg', 'exp_avg_sq')), 'sgd': (torch.optim.SGD, ()),
+               'sgdm': (torch.optim.SGD, ('momentum_buffer',)), 'sgdmom': (torch.optim.SGD, ('momentum_buffer',)),
+               'rmsprop': (torch.optim.RMSprop, ('square_avg',)), 'adagrad': (torch.optim.Adagrad, ('sum',))}
 
-    def __init__(self, module, names=None, world=1, rank=0, pieces=None, operand_dtype=None):
+    def __init__(self, module, names=None, world=1, rank=0, pieces=None, operand_dtype=None, method='adam'):
+        if method not in self.METHODS:
+            raise RuntimeError("Invalid optim method: " + str(method))
+        self.method = method
+        self.state_names = self.METHODS[method][1]
         params = dict(module.named_parameters())
         # module.parameters() in registration order: the order torch.optim.Adam numbers its state in (export / import below)
         self.param_order = [(k, tuple(p.shape)) for k, p in params.items()]
@@ -81,8 +105,8 @@ class FlatArena(object):
         self.numel = off
         self.flat = torch.zeros(off, dtype=torch.float32, device=dev)
         self.grad = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.exp_avg = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.exp_avg_sq = torch.zeros(off, dtype=torch.float32, device=dev)
+        for s in self.state_names:                  # only what the method uses: sgd has no state arena at all
+            setattr(self, s, torch.zeros(off, dtype=torch.float32, device=dev))
         self.scratch = torch.zeros(1024 + 8, dtype=torch.float32, device=dev)    # sqnorm partials + result
         self.scalars = self.grad[self.scalars_off:self.scalars_off + self.SCALAR_SLOTS] if pieces else None
         self.grad_views = {}
@@ -101,7 +125,7 @@ class FlatArena(object):
         self.g16 = None                 # bf16 staging of the gradient pieces that sharded_step(half=...) exchanges in bf16 (made on first use)
         self.masters_stale = False
         if self.operand_dtype is not None:
-            # (the whole arena's length: uic_adam_step_ranges leaves the operand copy of EVERY element it updates, the replicated
+            # (the whole arena's length: uic_optim_step_ranges leaves the operand copy of EVERY element it updates, the replicated
             # tail's too -- only the sharded region [0, repl_off) is ever gathered or read)
             self.w16 = torch.zeros(self.numel, dtype=self.operand_dtype, device=dev)
             self.sync_operand_copy()
@@ -135,20 +159,42 @@ class FlatArena(object):
             out.append((self.repl_off, self.repl_end))
         return out
 
-    def adam_owned(self, lr, betas, eps, step, grad_scale=1.0, max_norm=0.0, sqnorm=None, guard=None, ranges=None):
-        """uic_adam_step_ranges on owned_ranges() (or the given subset of them); in operand-dtype mode the updated shard is also
-        written to w16 (the rank's contribution to the all-gather)."""
+    @property
+    def states(self):
+        """The method's state arenas (none, one or two), in the order of the kernels' s0 / s1."""
+        return [getattr(self, s) for s in self.state_names]
+
+    def hyper(self, betas, eps):
+        """(alpha, beta, eps) as the reference's create_optimizer hands (optim_alpha, optim_beta, optim_epsilon) to this arena's
+        method (P/misc/optimizer.py:61-71): Adam's betas; optim_alpha alone is the momentum of sgdm / sgdmom and RMSprop's alpha;
+        Adagrad is not given optim_epsilon and keeps torch's own 1e-10."""
+        return float(betas[0]), float(betas[1]), 1e-10 if self.method == 'adagrad' else float(eps)
+
+    def _step_args(self, lr, betas, eps, step, grad_scale, max_norm, sqnorm, guard, weight_decay):
+        """(uic_optim_config by reference, p, g, s0, s1) of one step of this arena's method."""
+        import ctypes as C
+        clip = bool(max_norm and max_norm > 0)
+        if clip and weight_decay and sqnorm.numel() < 2:
+            sqnorm = torch.cat([sqnorm.reshape(1), sqnorm.new_zeros(1)])      # (a decayed step reads the norm as a float pair)
+        alpha, beta, eps = self.hyper(betas, eps)
+        cfg = _lib.OptimConfig(_lib.OPTIM_METHODS[self.method], lr, alpha, beta, eps, float(weight_decay or 0.0), step, grad_scale,
+                               float(max_norm) if clip else 0.0, ptr(sqnorm) if clip else None, ptr(guard))
+        s = [ptr(t) for t in self.states] + [None, None]
+        return C.byref(cfg), ptr(self.flat), ptr(self.grad), s[0], s[1]
+
+    def adam_owned(self, lr, betas, eps, step, grad_scale=1.0, max_norm=0.0, sqnorm=None, guard=None, ranges=None, weight_decay=0.0):
+        """uic_optim_step_ranges -- the arena's method, whatever the name says -- on owned_ranges() (or the given subset of
+        them); in operand-dtype mode the updated shard is also written to w16 (the rank's contribution to the
+        all-gather)."""
         import ctypes as C
         rg = self.owned_ranges() if ranges is None else list(ranges)
         if not rg:
             return
         lo = (C.c_uint64 * len(rg))(*[a for a, _ in rg])
         hi = (C.c_uint64 * len(rg))(*[b for _, b in rg])
-        clip = bool(max_norm and max_norm > 0)
-        check(_lib.load().uic_adam_step_ranges(ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), len(rg), lo, hi,
-                                               lr, betas[0], betas[1], eps, step, grad_scale, float(max_norm) if clip else 0.0,
-                                               ptr(sqnorm) if clip else None, ptr(guard), ptr(self.w16),
-                                               _lib.dtype_id("bf16") if self.w16 is not None else 0, stream()), "adam_step_ranges")
+        check(_lib.load().uic_optim_step_ranges(*self._step_args(lr, betas, eps, step, grad_scale, max_norm, sqnorm, guard, weight_decay),
+                                                len(rg), lo, hi, ptr(self.w16), _lib.dtype_id("bf16") if self.w16 is not None else 0,
+                                                stream()), "optim_step_ranges")
         if self.w16 is not None and self.world > 1:
             self.masters_stale = True
 
@@ -163,14 +209,14 @@ class FlatArena(object):
         return outs.sum().reshape(1)
 
     def sharded_step(self, ex, lr, betas, eps, step, grad_scale=1.0, max_norm=0.0, wait_piece=None, comm=None, gather_async=False,
-                     early_guard=None, pipeline=(), half=()):
+                     early_guard=None, pipeline=(), half=(), weight_decay=0.0):
         """One optimizer step of the sharded exchange on this arena (gradients final or becoming final on the current stream):
 
           1. reduce-scatter every piece -- piece i on the communication stream `comm` behind wait_piece(comm raw stream, i) when
              that returns True (the piece becomes final while the backward pass still runs), else on the current stream;
           2. one small all-reduce of the replicated tail + the scalar slots the caller filled beforehand ([0] loss, [1] status
              flag, [3] the next batch's mask sum; [2] is used here for the clip norm);
-          3. Adam on owned_ranges(), clipped by the GLOBAL gradient norm when max_norm > 0, skipped on the device on every rank when
+          3. the optimizer step (the arena's method; betas = (optim_alpha, optim_beta), weight_decay) on owned_ranges(), clipped by the GLOBAL gradient norm when max_norm > 0, skipped on the device on every rank when
              the summed status flag is non-zero;
           4. all-gather of the updated weights (operand-dtype copy or the f32 masters in place), last piece first -- the order a
              forward pass consumes them in.  gather_async: on `comm`, one event per piece, the current stream does NOT wait
@@ -221,7 +267,7 @@ class FlatArena(object):
                 else:
                     ex.reduce_scatter(self.grad, *self.pieces[i])
                 if early and i in pipeline and guard is not None:
-                    self.adam_owned(lr, betas, eps, step, grad_scale, guard=guard, ranges=[self.shard(i)])
+                    self.adam_owned(lr, betas, eps, step, grad_scale, guard=guard, ranges=[self.shard(i)], weight_decay=weight_decay)
                     ex.all_gather(buf, *self.pieces[i])
                     e = torch.cuda.Event()
                     e.record(comm)
@@ -248,7 +294,7 @@ class FlatArena(object):
         rg = [self.shard(i) for i in rest]
         if self.repl_end > self.repl_off:
             rg.append((self.repl_off, self.repl_end))
-        self.adam_owned(lr, betas, eps, step, grad_scale, max_norm if clip else 0.0, sq, guard=pair[1:2], ranges=rg)
+        self.adam_owned(lr, betas, eps, step, grad_scale, max_norm if clip else 0.0, sq, guard=pair[1:2], ranges=rg, weight_decay=weight_decay)
         if gather_async and comm is not None:
             ev = torch.cuda.Event()
             ev.record(cur)
@@ -277,51 +323,93 @@ class FlatArena(object):
 
     # ------------------------------------------------------------------ checkpoints ("Checkpoints")
     def gather_moments(self, exchange):
-        """All-gather exp_avg / exp_avg_sq of every piece in place, as gather_masters does for `flat` (a collective: every rank
-        calls it): a rank's Adam moments exist only on its owned_ranges().  Afterwards the slices this rank does NOT own hold the
-        owners' moments of that moment; they go stale as training continues and nothing reads them -- Adam runs on owned_ranges()
-        only, and every export gathers again first."""
+        """All-gather the method's state arenas (Adam: exp_avg / exp_avg_sq; sgd: nothing) of every piece in place, as
+        gather_masters does for `flat` (a collective: every rank calls it): a rank's optimizer state exists only on its
+        owned_ranges().  Afterwards the slices this rank does NOT own hold the owners' state of that moment; they go stale as
+        training continues and nothing reads them -- the step runs on owned_ranges() only, and every export gathers again first."""
         if self.pieces and exchange is not None and exchange.world_size > 1:
-            for buf in (self.exp_avg, self.exp_avg_sq):
+            for buf in self.states:
                 for g in range(len(self.pieces)):
                     exchange.all_gather(buf, *self.pieces[g])
 
-    def export_adam_state(self, lr, betas, eps, step, exchange=None, collect=True):
-        """The arena's Adam state in the layout of torch.optim.Adam.state_dict() over module.parameters() -- what the reference
-        saves (P/trainer.py:103-104) and reads back (P/misc/optimizer.py:80-87): entry i is the i-th parameter in REGISTRATION
-        order (not the arena's), state[i] = {'step', 'exp_avg', 'exp_avg_sq'} with host tensors of the parameter's shape.  A
-        parameter outside the arena keeps its index and gets no state; before the first step there is no state at all, as in
-        torch.  The param_groups keys are the installed torch's own, so torch.optim.Adam.load_state_dict takes the result.
-        Sharded arenas all-gather the moments first: a collective, every rank calls this; collect=False (a rank that writes no
-        file) stops there and returns None."""
+    def export_optimizer_state(self, lr, betas, eps, step, exchange=None, collect=True, weight_decay=0):
+        """The arena's optimizer state in the layout of torch.optim.<Class>.state_dict() over module.parameters(), <Class> being
+        what the reference builds for the arena's method (P/misc/optimizer.py:59-74) -- what the reference saves
+        (P/trainer.py:103-104) and reads back (P/misc/optimizer.py:80-87): entry i is the i-th parameter in REGISTRATION order
+        (not the arena's), state[i] = Adam {'step', 'exp_avg', 'exp_avg_sq'}, sgdm / sgdmom {'momentum_buffer'}, rmsprop
+        {'step', 'square_avg'}, adagrad {'step', 'sum'}, sgd nothing, with host tensors of the parameter's shape.  A parameter
+        outside the arena keeps its index and gets no state; before the first step there is no state at all, as in torch (whose
+        Adagrad alone makes its state when it is built: step 0, zero sums).  The param_groups keys are the installed torch's
+        own, so <Class>.load_state_dict takes the result.  betas = (optim_alpha, optim_beta), see hyper().  Sharded arenas
+        all-gather the state first: a collective, every rank calls this; collect=False (a rank that writes no file) stops there
+        and returns None."""
         self.gather_moments(exchange)
         if not collect:
             return None
-        return self.adam_state_from(self.exp_avg.detach().cpu(), self.exp_avg_sq.detach().cpu(), lr, betas, eps, step, clone=True)
+        return self.optimizer_state_from([t.detach().cpu() for t in self.states], lr, betas, eps, step, weight_decay, clone=True)
 
-    def adam_state_from(self, m, v, lr, betas, eps, step, clone=False):
-        """export_adam_state's dict from host copies `m` / `v` of exp_avg / exp_avg_sq (at least the arena's first scalars_off
-        elements; Trainer's checkpoint snapshot hands in its pinned buffers).  clone=False: the state tensors are views of m / v."""
-        group = dict(torch.optim.Adam([torch.nn.Parameter(torch.zeros(1))]).state_dict()['param_groups'][0])
-        group.update(lr=float(lr), betas=(float(betas[0]), float(betas[1])), eps=float(eps), weight_decay=0,
-                     params=list(range(len(self.param_order))))
+    def optimizer_state_from(self, rows, lr, betas, eps, step, weight_decay=0, clone=False):
+        """export_optimizer_state's dict from host copies `rows` of the state arenas (at least the arena's first scalars_off
+        elements each; Trainer's checkpoint snapshot hands in its pinned buffers).  clone=False: the state tensors are views of
+        the rows."""
+        cls = self.METHODS[self.method][0]
+        alpha, beta, eps = self.hyper(betas, eps)
+        probe = [torch.nn.Parameter(torch.zeros(1))]
+        made = {'adam': lambda: cls(probe, lr, (alpha, beta), eps, weight_decay=weight_decay),
+                'sgd': lambda: cls(probe, lr, weight_decay=weight_decay),
+                'sgdm': lambda: cls(probe, lr, alpha, weight_decay=weight_decay),
+                'sgdmom': lambda: cls(probe, lr, alpha, weight_decay=weight_decay, nesterov=True),
+                'rmsprop': lambda: cls(probe, lr, alpha, eps, weight_decay=weight_decay),
+                'adagrad': lambda: cls(probe, lr, weight_decay=weight_decay)}[self.method]()
+        group = dict(made.state_dict()['param_groups'][0])
+        group.update(lr=float(lr), params=list(range(len(self.param_order))))
+        has_step = self.method in ('adam', 'rmsprop', 'adagrad')
         state = {}
-        if step > 0:
+        if self.state_names and (step > 0 or self.method == 'adagrad'):
             for i, (k, shape) in enumerate(self.param_order):
                 if k not in self.offsets:
                     continue
                 o, n = self.offsets[k], self.params[k].numel()
-                em, ev = m[o:o + n].view(shape), v[o:o + n].view(shape)
-                state[i] = {'step': torch.tensor(float(step)), 'exp_avg': em.clone() if clone else em,
-                            'exp_avg_sq': ev.clone() if clone else ev}
+                st = {'step': torch.tensor(float(step))} if has_step else {}
+                for name, row in zip(self.state_names, rows):
+                    t = row[o:o + n].view(shape)
+                    st[name] = t.clone() if clone else t
+                state[i] = st
         return {'state': state, 'param_groups': [group]}
 
-    def import_adam_state(self, sd):
-        """Inverse of export_adam_state.  Entries are matched BY POSITION in the concatenated param_groups[*]['params'] -- torch 0.3
-        wrote id(p) there --, 'step' may be an int or a tensor.  Raises ValueError (nothing is written then) on a shape mismatch or
-        when the parameters' steps differ: the arena has one step.  The whole arena is filled on every rank, whatever world size
-        wrote the file; the operand-dtype copy is rebuilt from the masters (load the weights first) and masters_stale is cleared.
-        Returns (step, lr)."""
+    def adam_state_from(self, m, v, lr, betas, eps, step, clone=False):
+        """optimizer_state_from for an Adam arena, from host copies of exp_avg / exp_avg_sq."""
+        return self.optimizer_state_from([m, v], lr, betas, eps, step, clone=clone)
+
+    @staticmethod
+    def method_of(sd):
+        """The method that wrote an optimizer state dict, from the hyper-parameters only its torch.optim class keeps in
+        param_groups (any torch version's); a dict with none of them (hand-made) is told by its state tensors, else Adam's."""
+        g = sd['param_groups'][0]
+        if 'betas' in g:
+            return 'adam'
+        if 'alpha' in g:
+            return 'rmsprop'
+        if 'lr_decay' in g:
+            return 'adagrad'
+        if 'momentum' in g:
+            return 'sgd' if not g['momentum'] else ('sgdmom' if g.get('nesterov') else 'sgdm')
+        keys = set().union(*[set(st) for st in sd['state'].values()]) if sd['state'] else set()
+        for method in ('rmsprop', 'adagrad', 'sgdm'):
+            if FlatArena.METHODS[method][1][0] in keys:
+                return method
+        return 'adam'
+
+    def import_optimizer_state(self, sd):
+        """Inverse of export_optimizer_state.  Entries are matched BY POSITION in the concatenated param_groups[*]['params'] --
+        torch 0.3 wrote id(p) there --, 'step' may be an int or a tensor.  Raises ValueError (nothing is written then) when the
+        file was written by another method than the arena's (method_of), on a shape mismatch or when the parameters' steps
+        differ: the arena has one step.  The whole arena is filled on every rank, whatever world size wrote the file; the
+        operand-dtype copy is rebuilt from the masters (load the weights first) and masters_stale is cleared.  Returns
+        (step, lr); step is 0 for sgd / sgdm / sgdmom, whose files hold none."""
+        theirs = self.method_of(sd)
+        if theirs != self.method:
+            raise ValueError("the optimizer state was written by method '%s', this arena runs '%s'" % (theirs, self.method))
         keys = [key for g in sd['param_groups'] for key in g['params']]
         if len(keys) != len(self.param_order):
             raise ValueError("optimizer state for %d parameters, the module has %d" % (len(keys), len(self.param_order)))
@@ -330,26 +418,30 @@ class FlatArena(object):
             st = sd['state'].get(key)
             if st is None or k not in self.offsets:
                 continue
-            for f in ('exp_avg', 'exp_avg_sq'):
+            for f in self.state_names:
                 if tuple(st[f].shape) != shape:
                     raise ValueError("optimizer state %r (parameter %s): %s has shape %s, the parameter %s"
                                      % (key, k, f, tuple(st[f].shape), shape))
-            s = int(st['step'].item()) if torch.is_tensor(st['step']) else int(st['step'])
-            if first is None:
-                step, first = s, (key, k)
-            elif s != step:
-                raise ValueError("optimizer state %r (parameter %s) is at step %d, %r (parameter %s) at step %d: the arena has one "
-                                 "step" % (key, k, s, first[0], first[1], step))
+            if 'step' in st:
+                s = int(st['step'].item()) if torch.is_tensor(st['step']) else int(st['step'])
+                if first is None:
+                    step, first = s, (key, k)
+                elif s != step:
+                    raise ValueError("optimizer state %r (parameter %s) is at step %d, %r (parameter %s) at step %d: the arena has one "
+                                     "step" % (key, k, s, first[0], first[1], step))
             found.append((k, st))
-        self.exp_avg.zero_()
-        self.exp_avg_sq.zero_()
+        for buf in self.states:
+            buf.zero_()
         for k, st in found:
             o, n = self.offsets[k], self.params[k].numel()
-            self.exp_avg[o:o + n].copy_(st['exp_avg'].reshape(-1))
-            self.exp_avg_sq[o:o + n].copy_(st['exp_avg_sq'].reshape(-1))
+            for f, buf in zip(self.state_names, self.states):
+                buf[o:o + n].copy_(st[f].reshape(-1))
         self.sync_operand_copy()
         self.masters_stale = False
         return step, float(sd['param_groups'][0]['lr'])
+
+    export_adam_state = export_optimizer_state        # (the names callers of Adam arenas use)
+    import_adam_state = import_optimizer_state
 
     def bind_grads(self):
         """Make every p.grad the arena view, so autograd accumulates in place."""
@@ -360,19 +452,20 @@ class FlatArena(object):
         self.grad.zero_()
         self.bind_grads()
 
-    def adam(self, lr, betas, eps, step, grad_scale=1.0, max_norm=0.0, guard=None):
-        """guard (optional, a device word): the update is skipped on the device when it is non-zero -- the status word of the
+    def adam(self, lr, betas, eps, step, grad_scale=1.0, max_norm=0.0, guard=None, weight_decay=0.0):
+        """One step of the arena's method, whatever the name says, over the whole arena (uic_optim_step).
+        betas = (optim_alpha, optim_beta), see hyper(); max_norm > 0: clipped by the global gradient norm, read on the device.
+        guard (optional, a device word): the update is skipped on the device when it is non-zero -- the status word of the
         persistent kernels, so that a timed-out launch's gradients never reach the weights (include/uic_hip.h)."""
         lib = _lib.load()
+        sq = None
         if max_norm and max_norm > 0:
-            sq = self.scratch[1024:1025]
-            check(lib.uic_grad_sqnorm(ptr(self.grad), self.numel, ptr(self.scratch), ptr(sq), stream()), "grad_sqnorm")
-            check(lib.uic_adam_step_clip_guarded(ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.numel,
-                                                 lr, betas[0], betas[1], eps, step, grad_scale, float(max_norm), ptr(sq), ptr(guard),
-                                                 stream()), "adam_step_clip_guarded")
-        else:
-            check(lib.uic_adam_step_guarded(ptr(self.flat), ptr(self.grad), ptr(self.exp_avg), ptr(self.exp_avg_sq), self.numel,
-                                            lr, betas[0], betas[1], eps, step, grad_scale, ptr(guard), stream()), "adam_step_guarded")
+            # (with decay the kernel forms the clip coefficient in double, from the norm accumulated in double: a float pair)
+            sq = self.scratch[1024:1026] if weight_decay else self.scratch[1024:1025]
+            norm = lib.uic_grad_sqnorm_f64 if weight_decay else lib.uic_grad_sqnorm
+            check(norm(ptr(self.grad), self.numel, ptr(self.scratch), ptr(sq), stream()), "grad_sqnorm")
+        check(lib.uic_optim_step(*self._step_args(lr, betas, eps, step, grad_scale, max_norm, sq, guard, weight_decay), self.numel, stream()),
+              "optim_step")
 
     def grad_norm(self):
         """Host value of the global gradient L2 norm (diagnostics; synchronises)."""
@@ -431,21 +524,12 @@ class Optim(object):
         self.nmt_warmup_steps = _get(opt, 'nmt_warmup_steps', 4000)
         self.nmt_betas = [0.9, 0.98]
 
-    @staticmethod
-    def _check_method(kind, method, weight_decay):
-        if method != 'adam':
-            raise NotImplementedError("only Adam is on the MI355X hot path (%s_optim=%s)" % (kind, method))
-        if weight_decay:
-            raise NotImplementedError("%s_weight_decay != 0 is not on the MI355X hot path" % kind)
-
     def set_parameters(self, i2t_model, nmt_model):
         if i2t_model is not None:
-            self._check_method('i2t', self.i2t_method, self.i2t_weight_decay)
             names = getattr(i2t_model, 'param_names', None)
-            self.i2t_arena = FlatArena(i2t_model, names)
+            self.i2t_arena = FlatArena(i2t_model, names, method=self.i2t_method)
             self.i2t_arena.bind_grads()
         if nmt_model is not None:
-            self._check_method('nmt', self.nmt_method, self.nmt_weight_decay)
             # arena order = the order in which uic_nmt_backward makes the gradients final (include/uic_hip.h,
             # uic_nmt_grad_ready_wait): generator first (before the decoder BPTT starts), the decoder side, the encoder last -- a
             # data-parallel run exchanges each piece while the backward pass computes the following ones
@@ -463,9 +547,9 @@ class Optim(object):
                 # sharded exchange with the f32 masters as the gathered weights (the pivot model's operand copies are cast from them
                 # by uic_nmt_forward_loss itself): reduce-scatter [generator | decoder | encoder], clipped Adam on this rank's third
                 # of a third, all-gather in place -- the bytes of one all-reduce, an eighth of the optimizer's work
-                self.nmt_arena = FlatArena(nmt_model, names, world=ex.world_size, rank=ex.rank, pieces=[gen, dec, enc])
+                self.nmt_arena = FlatArena(nmt_model, names, world=ex.world_size, rank=ex.rank, pieces=[gen, dec, enc], method=self.nmt_method)
             else:
-                self.nmt_arena = FlatArena(nmt_model, names)
+                self.nmt_arena = FlatArena(nmt_model, names, method=self.nmt_method)
             if names is not None and gen and dec and enc:
                 self.nmt_splits = [self.nmt_arena.offsets[dec[0]], self.nmt_arena.offsets[enc[0]]]
             self.nmt_arena.bind_grads()
@@ -498,7 +582,7 @@ class Optim(object):
                     self.exchange._sum(ig)
             self.last_i2t_guard = ig
             self.i2t_arena.adam(self.i2t_current_lr, (self.i2t_optim_alpha, self.i2t_optim_beta), self.i2t_optim_epsilon,
-                                self._i2t_steps, i2t_grad_scale, 0.0, guard=ig)
+                                self._i2t_steps, i2t_grad_scale, 0.0, guard=ig, weight_decay=self.i2t_weight_decay)
         if _get(self.opt, 'nmt_train_flag', 0) and self.nmt_arena is not None:
             if self.nmt_decay_method == "noam":
                 self.nmt_current_lr = self.nmt_lr * (self.opt.rnn_size ** (-0.5) *
@@ -535,7 +619,8 @@ class Optim(object):
                     return True
                 pair, _ = a.sharded_step(self.exchange, self.nmt_current_lr, (self.nmt_optim_alpha, self.nmt_optim_beta), self.nmt_optim_epsilon,
                                          self._nmt_steps, nmt_grad_scale, self.nmt_max_grad_norm, wait_piece=wait_piece,
-                                         comm=getattr(self, '_comm_stream', None) if overlap else None)
+                                         comm=getattr(self, '_comm_stream', None) if overlap else None,
+                                         weight_decay=self.nmt_weight_decay)
                 self.last_pair = pair                   # [summed loss (slot 0, filled by the caller), summed status flag]
                 self.last_guard = pair[1:2]
                 return
@@ -545,18 +630,20 @@ class Optim(object):
                 self.exchange._sum(guard)
             self.last_guard = guard
             self.nmt_arena.adam(self.nmt_current_lr, (self.nmt_optim_alpha, self.nmt_optim_beta), self.nmt_optim_epsilon,
-                                self._nmt_steps, nmt_grad_scale, self.nmt_max_grad_norm, guard=guard)
+                                self._nmt_steps, nmt_grad_scale, self.nmt_max_grad_norm, guard=guard, weight_decay=self.nmt_weight_decay)
 
     def state_dict(self, collect=True):
-        """Both arenas' Adam state (FlatArena.export_adam_state: the reference's optimizer_i2t / optimizer_nmt files, None for an
+        """Both arenas' optimizer state (FlatArena.export_optimizer_state: the reference's optimizer_i2t / optimizer_nmt files, None for an
         arena that was not built) plus what the reference keeps on the Optim object itself: the step counters and the current
         learning rates.  A collective under the sharded exchange: every rank calls it (collect=False: a rank that writes no file
         takes part in the gathers and gets None for the arenas)."""
         a, n = self.i2t_arena, self.nmt_arena
-        return {'i2t': None if a is None else a.export_adam_state(self.i2t_current_lr, (self.i2t_optim_alpha, self.i2t_optim_beta),
-                                                                  self.i2t_optim_epsilon, self._i2t_steps, self.exchange, collect),
-                'nmt': None if n is None else n.export_adam_state(self.nmt_current_lr, (self.nmt_optim_alpha, self.nmt_optim_beta),
-                                                                  self.nmt_optim_epsilon, self._nmt_steps, self.exchange, collect),
+        return {'i2t': None if a is None else a.export_optimizer_state(self.i2t_current_lr, (self.i2t_optim_alpha, self.i2t_optim_beta),
+                                                                       self.i2t_optim_epsilon, self._i2t_steps, self.exchange, collect,
+                                                                       self.i2t_weight_decay),
+                'nmt': None if n is None else n.export_optimizer_state(self.nmt_current_lr, (self.nmt_optim_alpha, self.nmt_optim_beta),
+                                                                       self.nmt_optim_epsilon, self._nmt_steps, self.exchange, collect,
+                                                                       self.nmt_weight_decay),
                 **self.counters()}
 
     def counters(self):
@@ -572,7 +659,7 @@ class Optim(object):
         for kind, arena in (('i2t', self.i2t_arena), ('nmt', self.nmt_arena)):
             if arena is None or sd.get(kind) is None:
                 continue
-            step, lr = arena.import_adam_state(sd[kind])
+            step, lr = arena.import_optimizer_state(sd[kind])
             setattr(self, '_%s_steps' % kind, int(sd.get('_%s_steps' % kind, step)))
             setattr(self, '%s_current_lr' % kind, float(sd.get('%s_current_lr' % kind, lr)))
         self._step = int(sd.get('_step', max(self._i2t_steps, self._nmt_steps)))

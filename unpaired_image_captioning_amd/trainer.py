@@ -14,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, models
-from ._lib import check, ptr, stream
+from ._lib import check
 from .topdown_engine import live_counts
 from .misc.optimizer import FlatArena, Optim  # noqa: F401
 from .parallel_exchange import GradientExchange
@@ -126,10 +126,11 @@ class Trainer(object):
         self.i2t_current_lr = self.lr
         self.betas = (getattr(opt, 'i2t_optim_alpha', 0.9), getattr(opt, 'i2t_optim_beta', 0.999))
         self.eps = getattr(opt, 'i2t_optim_epsilon', 1e-8)
-        if getattr(opt, 'i2t_optim', 'adam') != 'adam':
-            raise NotImplementedError("only Adam is on the MI355X hot path (i2t_optim=%s)" % opt.i2t_optim)
-        if getattr(opt, 'i2t_weight_decay', 0):
-            raise NotImplementedError("i2t_weight_decay != 0 is not on the MI355X hot path")
+        # --i2t_optim / --i2t_weight_decay as Optim.init_i2t reads them (P/misc/optimizer.py:26-38,59-74): betas = (optim_alpha,
+        # optim_beta) are Adam's, optim_alpha alone the momentum or RMSprop's alpha (FlatArena.hyper); build_optimizer rejects an
+        # unknown method
+        self.method = getattr(opt, 'i2t_optim', 'adam')
+        self.weight_decay = getattr(opt, 'i2t_weight_decay', 0)
         self._step = 0
         self.arena = None
         self.last_loss = None
@@ -207,14 +208,14 @@ class Trainer(object):
             self.piece_groups = [gid for (g, gid), p in zip(cand, pieces) if p]
             op_dtype = _lib.TORCH_DTYPE[eng.dtype]
             self.arena = FlatArena(self.i2t_model, [k for g, _ in cand for k in g], world=ex.world_size, rank=ex.rank,
-                                   pieces=[p for p in pieces if p], operand_dtype=op_dtype)
+                                   pieces=[p for p in pieces if p], operand_dtype=op_dtype, method=self.method)
             self.arena_splits = []
             eng.gathered = _GatheredWeights(self.arena, mats)
             self._next_den = None
             arena = self.arena
             self.i2t_model._stale_masters = lambda: arena.masters_stale
         else:
-            self.arena = FlatArena(self.i2t_model, first + lstm_w + early + late)
+            self.arena = FlatArena(self.i2t_model, first + lstm_w + early + late, method=self.method)
             self.arena_splits = [self.arena.offsets[g[0]] for g in groups[1:]] if first and all(groups[1:]) else []
             if eng is not None:
                 eng.gathered = None
@@ -409,7 +410,8 @@ class Trainer(object):
         half = tuple(i for i in range(len(a.pieces)) if i not in pipe) if getattr(self.opt, 'bf16_gradient_exchange', 0) else ()
         pair, events = a.sharded_step(self.exchange, self.i2t_current_lr, self.betas, self.eps, self._step, grad_scale,
                                       wait_piece=wait_piece, comm=self._comm(dev), gather_async=True,
-                                      early_guard=_lib.status_words(dev) if pipe else None, pipeline=pipe, half=half)
+                                      early_guard=_lib.status_words(dev) if pipe else None, pipeline=pipe, half=half,
+                                      weight_decay=self.weight_decay)
         self._guard_pair = pair
         if next_den_local is not None:
             self._next_den = (float(next_den_local), sc[3:4].reciprocal())
@@ -438,8 +440,9 @@ class Trainer(object):
             a.gather_masters(self.exchange)
 
     def _guarded_adam(self, loss, grad_scale):
-        """Adam on the flat arena, skipped ON THE DEVICE if a persistent recurrence launch of this step timed out
-        (uic_adam_step_guarded reads the status word the kernels set): a bad step never reaches the weights or the moments.
+        """The optimizer step (--i2t_optim, FlatArena.adam) on the flat arena, skipped ON THE DEVICE if a persistent recurrence
+        launch of this step timed out (the kernel reads the status word the kernels set, uic_optim_config.skip_if_nonzero): a bad
+        step never reaches the weights or the optimizer state.
         Data parallel: [loss, status] travel in ONE 2-float all-reduce issued after the gradient exchange, so the returned loss
         is the sum over the ranks and every rank skips (and later raises, _finish_step) together.  Returns the loss, a device
         scalar."""
@@ -456,9 +459,7 @@ class Trainer(object):
             guard, loss = pair[1:], pair[0]
         else:
             guard = status
-        check(_lib.load().uic_adam_step_guarded(ptr(a.flat), ptr(a.grad), ptr(a.exp_avg), ptr(a.exp_avg_sq), a.numel,
-                                                self.i2t_current_lr, self.betas[0], self.betas[1], self.eps, self._step,
-                                                grad_scale, ptr(guard), stream()), "adam_step_guarded")
+        a.adam(self.i2t_current_lr, self.betas, self.eps, self._step, grad_scale, guard=guard, weight_decay=self.weight_decay)
         return loss
 
     def _raise_if_timed_out(self, cause):
@@ -898,23 +899,24 @@ class Trainer(object):
     class _Snapshot(object):
         """What one model contributes to a checkpoint, copied twice: device-to-device on the step's stream into `dev` (the step
         goes on and changes the arena), from there to the pinned `host` buffers on the copy stream.  Rows of dev / host: the
-        arena's flat, exp_avg, exp_avg_sq up to the scalar slots.  `extra`: state_dict entries that do not live in the arena -- the
-        BatchNorm buffers -- as {key: [device copy, pinned copy]}.  All buffers are allocated once and reused by every save."""
+        arena's flat and its state arenas (FlatArena.states: two for Adam, none for sgd) up to the scalar slots.  `extra`:
+        state_dict entries that do not live in the arena -- the BatchNorm buffers -- as {key: [device copy, pinned copy]}.  All buffers are allocated once and reused by every save."""
 
         def __init__(self, arena):
             self.n = arena.scalars_off if arena is not None else 0
+            self.rows = 1 + len(arena.states) if arena is not None else 0
             self.dev = self.host = None
             if arena is not None:
-                self.dev = torch.empty(3, self.n, dtype=torch.float32, device=arena.flat.device)
+                self.dev = torch.empty(self.rows, self.n, dtype=torch.float32, device=arena.flat.device)
                 # (one host tensor per row: torch.save writes a view's WHOLE storage, and the weights and the moments go to two files)
-                self.host = [torch.empty(self.n, dtype=torch.float32, pin_memory=arena.flat.is_cuda) for _ in range(3)]
+                self.host = [torch.empty(self.n, dtype=torch.float32, pin_memory=arena.flat.is_cuda) for _ in range(self.rows)]
             self.extra = {}
             self.layout = []
 
         def take(self, model, arena):
             """On the current stream: arena -> dev, and the layout of model.state_dict(): (key, arena offset or None, shape)."""
             if arena is not None:
-                for row, src in enumerate((arena.flat, arena.exp_avg, arena.exp_avg_sq)):
+                for row, src in enumerate([arena.flat] + arena.states):
                     self.dev[row].copy_(src[:self.n])
             self.layout = []
             for k, v in model.state_dict().items():
@@ -932,7 +934,7 @@ class Trainer(object):
         def to_host(self):
             """On the copy stream, behind the event that follows take()."""
             if self.dev is not None:
-                for row in range(3):
+                for row in range(self.rows):
                     self.host[row].copy_(self.dev[row], non_blocking=True)
             for k, off, _ in self.layout:
                 if off is None:
@@ -985,15 +987,20 @@ class Trainer(object):
                  'i2t_current_lr': float(self.i2t_current_lr), 'sc_flag': bool(self.sc_flag),
                  'ss_prob': float(getattr(self.i2t_model, 'ss_prob', 0.0)) if self.i2t_model is not None else 0.0,
                  'optim': None if o is None else o.counters()}
+        # (optional keys: a file without them was written when every arena ran Adam)
+        if self.arena is not None:
+            state['i2t_optim'] = self.arena.method
+        if nmt:
+            state['nmt_optim'] = o.nmt_arena.method
         if not writer:
             return                   # one writer: the ranks hold identical weights
-        # (kind, model, arena, Adam's lr / betas / eps / step for the optimizer file)
+        # (kind, model, arena, the optimizer's lr / betas / eps / step / weight decay for the optimizer file)
         jobs = []
         if self.i2t_model is not None:
-            jobs.append(('i2t', self.i2t_model, self.arena, (self.i2t_current_lr, self.betas, self.eps, self._step)))
+            jobs.append(('i2t', self.i2t_model, self.arena, (self.i2t_current_lr, self.betas, self.eps, self._step, self.weight_decay)))
         if nmt:
             jobs.append(('nmt', self.nmt_model, o.nmt_arena, (o.nmt_current_lr, (o.nmt_optim_alpha, o.nmt_optim_beta), o.nmt_optim_epsilon,
-                                                             o._nmt_steps)))
+                                                             o._nmt_steps, o.nmt_weight_decay)))
         snaps = self.__dict__.setdefault('_snapshots', {})
         with torch.no_grad():
             for kind, model, arena, _ in jobs:
@@ -1028,10 +1035,10 @@ class Trainer(object):
             if done is not None:
                 done.synchronize()
             os.makedirs(path, exist_ok=True)
-            for kind, arena, snap, (lr, betas, eps, step) in files:
+            for kind, arena, snap, (lr, betas, eps, step, wd) in files:
                 self._write(snap.state_dict(), os.path.join(path, 'model_%s%s.pth' % (kind, tag)))
                 if arena is not None:
-                    self._write(arena.adam_state_from(snap.host[1], snap.host[2], lr, betas, eps, step),
+                    self._write(arena.optimizer_state_from(snap.host[1:], lr, betas, eps, step, wd),
                                 os.path.join(path, 'optimizer_%s%s.pth' % (kind, tag)))
             state['seed_counters'] = self._seed_counters_end(kinds, rows)
             self._write(state, os.path.join(path, 'trainer_state' + tag + '.pth'))
@@ -1077,6 +1084,15 @@ class Trainer(object):
                              % (tag, state.get('format_version'), self.STATE_VERSION))
         if state is None:
             warnings.warn("load_models: no trainer_state%s.pth under %s -- counters and seeds start afresh" % (tag, path))
+        if state is not None:
+            # before anything is written: a checkpoint of another --i2t_optim / --nmt_optim does not continue under this one
+            # (for the models whose files are there; a state without the key was written when every arena ran Adam)
+            for kind, method in (('i2t', self.method if self.i2t_model is not None else None),
+                                 ('nmt', self.optim.nmt_method if getattr(self, 'nmt_model', None) is not None else None)):
+                theirs = state.get(kind + '_optim', 'adam')
+                if method is not None and theirs != method and os.path.isfile(os.path.join(path, 'model_%s%s.pth' % (kind, tag))):
+                    raise ValueError("trainer_state%s.pth was written with %s_optim='%s', this run is configured with '%s'"
+                                     % (tag, kind, theirs, method))
         seeds = state['seed_counters'] if state is not None else {}
         rank = self.exchange.rank
 
@@ -1098,11 +1114,12 @@ class Trainer(object):
             self.i2t_model.load_state_dict(sd)   # (in place: every parameter is its view of the arena)
             osd = self._read(path, ['optimizer_i2t' + tag + '.pth', 'i2t_optimizer.pth'])
             if osd is not None:
-                self._step, self.i2t_current_lr = a.import_adam_state(osd)
+                self._step, self.i2t_current_lr = a.import_optimizer_state(osd)
             else:
-                warnings.warn("load_models: no optimizer_i2t%s.pth / i2t_optimizer.pth under %s -- weights only, fresh Adam" % (tag, path))
-                a.exp_avg.zero_()
-                a.exp_avg_sq.zero_()
+                warnings.warn("load_models: no optimizer_i2t%s.pth / i2t_optimizer.pth under %s -- weights only, fresh %s"
+                              % (tag, path, 'Adam' if a.method == 'adam' else a.method))
+                for buf in a.states:
+                    buf.zero_()
                 a.sync_operand_copy()
                 a.masters_stale = False
                 self._step, self.i2t_current_lr = 0, self.lr
@@ -1127,10 +1144,11 @@ class Trainer(object):
                 raise ValueError("the NMT optimizer file under %s is not a state dict" % path)
             counters = dict(state['optim']) if (state is not None and state.get('optim') and osd is not None) else {}
             if osd is None:
-                warnings.warn("load_models: no optimizer_nmt%s.pth / nmt_optimizer.pth under %s -- weights only, fresh Adam" % (tag, path))
                 n = self.optim.nmt_arena
-                n.exp_avg.zero_()
-                n.exp_avg_sq.zero_()
+                warnings.warn("load_models: no optimizer_nmt%s.pth / nmt_optimizer.pth under %s -- weights only, fresh %s"
+                              % (tag, path, 'Adam' if n.method == 'adam' else n.method))
+                for buf in n.states:
+                    buf.zero_()
                 self.optim._step = self.optim._nmt_steps = 0
                 self.optim.nmt_current_lr = self.optim.nmt_lr
             else:
