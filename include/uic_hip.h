@@ -977,6 +977,42 @@ int uic_bleu_scores(const int64_t* hyp, int32_t n_hyp, int32_t L, int32_t batch_
  * `scores` are the sampled captions, rows N..2N-1 the greedy baseline. */
 int uic_ciderd_reward(const double* scores, int32_t N, int32_t L, float weight, float* reward, void* stream);
 
+/* ---- language evaluation of the validation pass (eval_utils.language_eval, P/eval_utils.py:26-86, 'zh' branch) ----
+ * The three scorers of AI_Challenger/Evaluation/caption_eval/coco_caption/pycxevalcap/eval.py -- Bleu(4), Rouge(), Cider() --
+ * on integer token rows.  Every entry point takes the description of the work of uic_ciderd_scores (hyp, batch_size,
+ * seq_per_img, ref_tok, ref_start; the evaluation passes n_img, 1) plus
+ *   end_token   1: a caption's words are its tokens up to and including the first 0 (the reward's array_to_str);
+ *               0: its tokens BEFORE the first 0 (utils.decode_sequence) -- a row that begins with 0 is the empty caption.
+ * With end_token = 1, uic_langeval_cider and uic_langeval_bleu give the bits of uic_ciderd_scores / uic_bleu_scores.
+ * Precondition: every reference has at least one word.  L, Lr <= 64.
+ *
+ * Cider.compute_score (pycxevalcap/cider/cider_scorer.py:93-181), which equals CiderD(df='corpus'): the table holds
+ * log(max(1, df)) with df = the number of IMAGES whose reference set holds the n-gram (:93-104), ref_len = log(n_img) (:160). */
+int uic_langeval_cider(const int64_t* hyp, int32_t n_hyp, int32_t L, int32_t batch_size, int32_t seq_per_img,
+                       const int64_t* ref_tok, int32_t Lr, const int32_t* ref_start, int32_t n_img,
+                       const int32_t* slot_keys, const double* slot_vals, int64_t slots, double ref_len,
+                       const double* penalty, int32_t pen_half, int32_t end_token, double* scores, void* stream);
+/* BleuScorer.compute_score(option='closest') per hypothesis (pycxevalcap/bleu/bleu_scorer.py:199-240), both outputs optional
+ * (not both null):
+ *   comps [n_hyp, 10] int32   correct[0..3], guess[0..3], testlen, the closest reflen (ties: the shorter) -- the integers the
+ *                             corpus score sums (:222-228);
+ *   bleu  [4, n_hyp] f64      BLEU-1..4: the running product ** (1 / (k + 1)), times the brevity factor on every order (:230-239). */
+int uic_langeval_bleu(const int64_t* hyp, int32_t n_hyp, int32_t L, int32_t batch_size, int32_t seq_per_img,
+                      const int64_t* ref_tok, int32_t Lr, const int32_t* ref_start, int32_t n_img, int32_t end_token,
+                      int32_t* comps, double* bleu, void* stream);
+/* Rouge.calc_score (pycxevalcap/rouge/rouge.py:13-75): the exact LCS length with every reference of the image, prec = lcs / len_c
+ * and rec = lcs / len_r maximised SEPARATELY over the references, score = ((1 + beta2) prec rec) / (rec + beta2 prec) in f64 in
+ * that order, 0 when either maximum is 0.  beta2 is the host's 1.2 ** 2.  A caption without words counts as the one word ''
+ * ("".split(" "), :54): len_c = 1, lcs = 0.  scores [n_hyp] f64. */
+int uic_langeval_rouge_l(const int64_t* hyp, int32_t n_hyp, int32_t L, int32_t batch_size, int32_t seq_per_img,
+                         const int64_t* ref_tok, int32_t Lr, const int32_t* ref_start, int32_t n_img, int32_t end_token,
+                         double beta2, double* scores, void* stream);
+/* Corpus sums of n images in ONE launch: totals [10] int64 = the column sums of comps (exact; the corpus Bleu_1..4 are formed on
+ * the host from them by the expression of bleu_scorer.py:247-256), means [2] f64 = mean(rouge), mean(cider), each added in a
+ * fixed order (the same bits on every call). */
+int uic_langeval_reduce(const int32_t* comps, const double* rouge, const double* cider, int32_t n, int64_t* totals, double* means,
+                        void* stream);
+
 /* ---- input pipeline: batch assembly on the device --------------------------------------------------------------------
  * Replaces the per-image numpy work of DataLoader.__getitem__ (P/misc/dataloader/dataloader.py:302-331) and the padding /
  * masking of DataLoader.get_batch (:277-283).  The host packs the RAW per-image files back to back, once per image (no

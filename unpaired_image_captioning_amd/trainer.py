@@ -134,6 +134,12 @@ class Trainer(object):
         self._step = 0
         self.arena = None
         self.last_loss = None
+        # validation state (P/trainer.py:36-48): the caller may restore the best scores from `infos` before the first eval
+        self.i2t_eval_flag = getattr(opt, 'i2t_eval_flag', 1)
+        self.best_i2t_val_score = None
+        self.best_nmt_val_acc = None
+        self.best_flag_i2t = False
+        self.best_flag_nmt = False
 
     @staticmethod
     def _require_two_hw_queues(opt, functional=False):
@@ -851,6 +857,50 @@ class Trainer(object):
             raise _lib.PersistentTimeout("persistent NMT kernel timed out: this step's update was skipped (weights and moments unchanged); "
                                          "engine.recurrence |= _lib.REC_FWD_CHAIN selects per-step launches")
         return val
+
+    # ------------------------------------------------------------------ validation (P/trainer.py:195-215)
+    def eval(self, loader, coco_loader=None):
+        """Trainer.eval, captioner half: eval_utils.eval_split over the 'val' split -- teacher-forced loss, one decoded caption per
+        image, lang_stats scored on the device -- and the choice of the '-best' checkpoint: a strict `>` on CIDEr
+        (opt.language_eval == 1) or on -val_loss.  Sets i2t_val_loss, predictions, lang_stats, coco_lang_stats,
+        best_i2t_val_score and best_flag_i2t; the caller saves with save_models('-best' if the flag is set else '') and clears
+        the flag.  The NMT half is eval_nmt."""
+        from . import eval_utils
+        if self.exchange.world_size > 1:
+            raise NotImplementedError("Trainer.eval on %d ranks: a sharded validation pass needs collectives for the captions and "
+                                      "the losses; evaluate on one rank" % self.exchange.world_size)
+        self.predictions = []
+        eval_kwargs = {'split': 'val', 'dataset': getattr(self.opt, 'input_json', '')}
+        eval_kwargs.update(vars(self.opt))
+        if self.i2t_eval_flag:
+            eval_tmp = eval_utils.eval_split(self.opt, loader, self.dp_i2t_model, None, eval_kwargs)
+            self.i2t_val_loss, self.predictions, self.lang_stats, _, _ = eval_tmp
+            self.coco_lang_stats = self.lang_stats
+            current_score = self.lang_stats['CIDEr'] if getattr(self.opt, 'language_eval', 0) == 1 else - self.i2t_val_loss
+            if self.best_i2t_val_score is None or current_score > self.best_i2t_val_score:
+                self.best_i2t_val_score = current_score
+                self.best_flag_i2t = True
+
+    def eval_nmt(self, batches):
+        """The NMT half of the validation pass (P/trainer.py:212-215, P/eval_utils.py:313-317): the given validation batches
+        through dp_nmt_model in eval mode and a fresh NMT_loss, no backward pass.  Sets nmt_valid_ppl, nmt_valid_acc,
+        best_nmt_val_acc and best_flag_nmt (strict `>`)."""
+        from .misc import criterion
+        crit = criterion.NMT_loss(self.opt, self.nmt_generator, self.nmt_loss, eval=True)
+        was_training = self.nmt_model.training
+        self.nmt_model.eval()
+        try:
+            with torch.no_grad():
+                for batch in batches:
+                    outputs, attn, _, _ = self.dp_nmt_model(batch.src, batch.tgt, batch.lengths, None)
+                    crit(None, batch, outputs, attn)
+        finally:
+            self.nmt_model.train(was_training)
+        self.nmt_valid_ppl = crit.total_stats.ppl()
+        self.nmt_valid_acc = crit.total_stats.accuracy()
+        if self.best_nmt_val_acc is None or self.nmt_valid_acc > self.best_nmt_val_acc:
+            self.best_nmt_val_acc = self.nmt_valid_acc
+            self.best_flag_nmt = True
 
     # ------------------------------------------------------------------ checkpoints (DESIGN.md, "Checkpoints")
     STATE_VERSION = 1
