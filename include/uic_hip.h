@@ -1053,6 +1053,98 @@ int uic_loader_inflate(const void* src, size_t n, void* dst, size_t m, int32_t f
  * declined. */
 int uic_loader_inflate_pair(const void* src0, size_t n0, void* dst0, size_t m0, const void* src1, size_t n1, void* dst1, size_t m1);
 
+/* ---------------------------------------------------------------- the Transformer captioner, eval mode (csrc/transformer.hip)
+ * The `transformer` caption model (P/models/TransformerModel.py; opts.py's default --caption_model): the teacher-forced
+ * forward pass and decoding.  Training (backward passes, dropout, label smoothing) is not built.
+ *
+ * The reference's LayerNorm (P/models/TransformerModel.py:91-103) over `rows` rows of length d:
+ * y = a_2 (x - mean) / (std + eps) + b_2 with the UNBIASED std (divisor d - 1) and eps added to the std -- not nn.LayerNorm.
+ * x [rows, ldx] f32 or bf16, y [rows, ldy] f32 or bf16 (any combination), statistics in f32, the row read once.
+ * 2 <= d <= 1024. */
+int uic_layernorm_std(int32_t in_dtype, int32_t out_dtype, const void* x, int32_t ldx, int32_t rows, int32_t d, const float* a_2,
+                      const float* b_2, float eps, void* y, int32_t ldy, void* stream);
+/* `attention` of MultiHeadedAttention.forward (P/models/TransformerModel.py:178-188, :203-222) for short sequences, h = 8
+ * heads, ONE launch: O[b, i, head] = softmax(Q[b, i, head] K[b / row_div, :, head]^T / sqrt(d_k)) V[b / row_div, :, head].
+ * Element (b, i, c) of an operand lies at b * batch_stride + i * ld + c (elements of `dtype`), c = head * d_k + e; the
+ * strides let q | k | v share a buffer and let decoding read its cache in place.  key_mask [B, ld_mask] bytes or NULL:
+ * key j of row b is masked where key_mask[b, j] == 0; causal != 0 also masks keys j > q_offset + i.  A masked score is
+ * the reference's finite -1e9 (masked_fill), so a fully masked row is uniform over all Sk keys.  row_div: the beams of an
+ * image share that image's K / V (B' = B / row_div batches of K and V).  Scores and softmax in f32; nothing of size
+ * [B, h, Sq, Sk] touches memory.  Supported: d_k a multiple of 8 in [8, 128], 1 <= Sk <= 128 (a head's whole K and V live in
+ * LDS), any Sq >= 1, B <= 65535; K / V strides multiples of 16 bytes.  Anything else is UIC_EARG. */
+int uic_mha_fwd(int32_t dtype, int32_t B, int32_t Sq, int32_t Sk, int32_t d_k, const void* Q, int32_t ldq, int64_t q_batch_stride,
+                const void* K, int32_t ldk, int64_t k_batch_stride, const void* V, int32_t ldv, int64_t v_batch_stride, void* O, int32_t ldo,
+                int64_t o_batch_stride, const uint8_t* key_mask, int32_t ld_mask, int32_t causal, int32_t q_offset, int32_t row_div,
+                void* stream);
+
+#define UIC_TRANSFORMER_MAX_LAYERS 8
+#define UIC_TRANSFORMER_HEADS 8            /* make_model(..., h=8) (P/models/TransformerModel.py:272-273) */
+typedef struct uic_transformer_dims {
+  int32_t N;         /* images */
+  int32_t R;         /* regions per image after clip_att (<= 128) */
+  int32_t D;         /* opt.att_feat_size */
+  int32_t d_model;   /* opt.input_encoding_size: a multiple of 64, <= 1024 */
+  int32_t d_ff;      /* opt.rnn_size (any value: zero-padded to a multiple of 8 in the derived copies) */
+  int32_t layers;    /* opt.num_layers, both stacks */
+  int32_t V1;        /* vocab_size + 1 */
+  int32_t T;         /* target positions the workspace holds: seq_length + 1 (<= 128) */
+  int32_t beam;      /* decode rows per image the workspace holds (1 unless beam search) */
+  int32_t dtype;
+  int32_t use_bn;    /* 0, 1, 2: the BatchNorm1d layers of att_embed, running statistics */
+} uic_transformer_dims;
+
+/* f32 masters under the reference's state_dict names.  enc[l] (model.encoder.layers.l): sublayer.0.norm.a_2, .b_2,
+ * sublayer.1.norm.a_2, .b_2, self_attn.linears.0-3 (weight, bias each), feed_forward.w_1 (weight, bias), w_2 (weight, bias).
+ * dec[l] (model.decoder.layers.l): sublayer.0-2.norm (a_2, b_2 each), self_attn.linears.0-3, src_attn.linears.0-3,
+ * feed_forward.w_1, w_2 (weight, bias each). */
+typedef struct uic_transformer_weights {
+  const float* att_w; const float* att_b;                           /* att_embed's Linear */
+  const float* att_bn0_w; const float* att_bn0_b; const float* att_bn0_rm; const float* att_bn0_rv;   /* att_embed.0, use_bn >= 1 */
+  const float* att_bn4_w; const float* att_bn4_b; const float* att_bn4_rm; const float* att_bn4_rv;   /* att_embed.4, use_bn == 2 */
+  const float* enc[UIC_TRANSFORMER_MAX_LAYERS][16];
+  const float* enc_norm_a; const float* enc_norm_b;                 /* model.encoder.norm */
+  const float* dec[UIC_TRANSFORMER_MAX_LAYERS][26];
+  const float* dec_norm_a; const float* dec_norm_b;                 /* model.decoder.norm */
+  const float* lut;                                                 /* model.tgt_embed.0.lut.weight [V1, d_model] */
+  const float* pe;                                                  /* model.tgt_embed.1.pe [1, 5000, d_model] (a buffer) */
+  const float* gen_w; const float* gen_b;                           /* model.generator.proj */
+} uic_transformer_weights;
+
+size_t uic_transformer_workspace_bytes(const uic_transformer_dims* d);
+size_t uic_transformer_derived_bytes(const uic_transformer_dims* d);
+/* The operand-dtype copies the calls below read: linears.0-2 of every attention stacked [3 d_model, d_model], w_1 / w_2 with
+ * d_ff zero-padded to a multiple of 8, att_embed's Linear with the affine part of BatchNorm1d(D) folded in.  Call after the
+ * masters change; N, R, T and beam of `d` play no part. */
+int uic_transformer_refresh_weights(const uic_transformer_dims* d, const uic_transformer_weights* w, void* derived, void* stream);
+/* _prepare_feature's source side and model.encode (P/models/TransformerModel.py:366-373, :53-54): att_embed on the valid
+ * regions (att_masks [N, R] f32 or NULL = all; padded regions are exact zeros, as pack_wrapper leaves them, and still pass
+ * through the encoder -- they are masked as keys only), the N encoder layers and the final norm.  The memory stays in the
+ * workspace; memory_out [N, R, d_model] f32 (optional) receives it. */
+int uic_transformer_encode(const uic_transformer_dims* d, const uic_transformer_weights* w, const void* derived, const float* att_feats,
+                           const float* att_masks, void* workspace, float* memory_out, void* stream);
+/* TransformerModel._forward (P/models/TransformerModel.py:390-428): encode, then the teacher-forced decoder over the first
+ * Tq columns of seq [N, ld_seq] int64 (the caller has dropped the last one: Tq = seq.size(1) - 1), key mask (seq > 0) with
+ * column 0 on, causal; generator and log-softmax.  logprobs_out [N, Tq, V1] f32: every position yields a row. */
+int uic_transformer_forward(const uic_transformer_dims* d, const uic_transformer_weights* w, const void* derived, const float* att_feats,
+                            const float* att_masks, const int64_t* seq, int32_t ld_seq, int32_t Tq, void* workspace, float* logprobs_out,
+                            void* stream);
+/* TransformerModel._sample (P/models/TransformerModel.py:520-576): <bos> = 0, arg-max (sample_max) or a multinomial draw from
+ * softmax(logits / temperature), a row emits 0 after its first 0.  A K/V cache per decoder layer: step t computes position t
+ * only.  All L steps are enqueued with no host read-back; once every row has finished the remaining entries stay 0, as after
+ * the reference's break.  seq [N, L] int64, seq_logp [N, L] f32. */
+int uic_transformer_sample(const uic_transformer_dims* d, const uic_transformer_weights* w, const void* derived, const float* att_feats,
+                           const float* att_masks, int32_t L, int32_t sample_max, float temperature, uint32_t seed, void* workspace,
+                           int64_t* seq, float* seq_logp, void* stream);
+/* TransformerModel._sample_beam over CaptionModel.beam_search (P/models/TransformerModel.py:444-475, P/models/CaptionModel.py:
+ * 33-177) with group_size = 1, all images at once: rows = (image, beam), beam_size == d->beam.  The beams of an image share its
+ * memory (row_div of the attention); the caches follow the surviving parents.  Outputs as uic_topdown_sample_beam. */
+int uic_transformer_sample_beam(const uic_transformer_dims* d, const uic_transformer_weights* w, const void* derived, const float* att_feats,
+                                const float* att_masks, int32_t L, int32_t beam_size, int32_t decoding_constraint, int32_t max_ppl,
+                                void* workspace, int64_t* seq, float* seq_logp, void* stream);
+/* The done list of the call above, read from the workspace right after it; layout as uic_topdown_beam_done_lists. */
+int uic_transformer_beam_done_lists(const uic_transformer_dims* d, void* workspace, int32_t L, int32_t beam_size, int32_t* done_count,
+                                    float* done_p, int64_t* done_seq, float* done_lp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -131,6 +131,81 @@ class DiscWeights(C.Structure):
                 ("hw_w", C.c_void_p), ("hw_b", C.c_void_p), ("out_w", C.c_void_p), ("out_b", C.c_void_p)]
 
 
+TRANSFORMER_MAX_LAYERS, TRANSFORMER_HEADS = 8, 8     # UIC_TRANSFORMER_MAX_LAYERS, UIC_TRANSFORMER_HEADS
+MHA_MAX_SK, MHA_MAX_DK, LAYERNORM_MAX_D = 128, 128, 1024    # what uic_mha_fwd / uic_layernorm_std accept (csrc/transformer.hip)
+
+
+class TransformerDims(C.Structure):
+    """uic_transformer_dims"""
+    _fields_ = [(n, C.c_int32) for n in ("N", "R", "D", "d_model", "d_ff", "layers", "V1", "T", "beam", "dtype", "use_bn")]
+
+
+class TransformerWeights(C.Structure):
+    """uic_transformer_weights"""
+    _fields_ = [(f, C.c_void_p) for f in ("att_w", "att_b", "att_bn0_w", "att_bn0_b", "att_bn0_rm", "att_bn0_rv",
+                                          "att_bn4_w", "att_bn4_b", "att_bn4_rm", "att_bn4_rv")] + \
+               [("enc", (C.c_void_p * 16) * TRANSFORMER_MAX_LAYERS), ("enc_norm_a", C.c_void_p), ("enc_norm_b", C.c_void_p),
+                ("dec", (C.c_void_p * 26) * TRANSFORMER_MAX_LAYERS), ("dec_norm_a", C.c_void_p), ("dec_norm_b", C.c_void_p),
+                ("lut", C.c_void_p), ("pe", C.c_void_p), ("gen_w", C.c_void_p), ("gen_b", C.c_void_p)]
+
+
+def _attn_keys(prefix):
+    return ["%s.linears.%d.%s" % (prefix, i, p) for i in range(4) for p in ("weight", "bias")]
+
+
+def _ffn_keys(prefix):
+    return ["%s.%s.%s" % (prefix, m, p) for m in ("w_1", "w_2") for p in ("weight", "bias")]
+
+
+def transformer_weight_keys(layers, use_bn=0):
+    """[(struct field, layer or None, slot or None, reference state_dict key)] of uic_transformer_weights: the slots of enc[l] / dec[l]
+    in the order include/uic_hip.h documents.  With use_bn >= 1 the Linear of att_embed moves to index 1
+    (P/models/TransformerModel.py:321-326)."""
+    lin = 1 if use_bn else 0
+    out = [("att_w", None, None, "att_embed.%d.weight" % lin), ("att_b", None, None, "att_embed.%d.bias" % lin)]
+    for i, f in ((0, "att_bn0"), (4, "att_bn4")):
+        if use_bn >= (1 if i == 0 else 2):
+            out += [(f + "_w", None, None, "att_embed.%d.weight" % i), (f + "_b", None, None, "att_embed.%d.bias" % i),
+                    (f + "_rm", None, None, "att_embed.%d.running_mean" % i), (f + "_rv", None, None, "att_embed.%d.running_var" % i)]
+    for l in range(layers):
+        pre = "model.encoder.layers.%d" % l
+        keys = ["%s.sublayer.%d.norm.%s" % (pre, i, p) for i in range(2) for p in ("a_2", "b_2")] + \
+            _attn_keys(pre + ".self_attn") + _ffn_keys(pre + ".feed_forward")
+        out += [("enc", l, i, k) for i, k in enumerate(keys)]
+        pre = "model.decoder.layers.%d" % l
+        keys = ["%s.sublayer.%d.norm.%s" % (pre, i, p) for i in range(3) for p in ("a_2", "b_2")] + \
+            _attn_keys(pre + ".self_attn") + _attn_keys(pre + ".src_attn") + _ffn_keys(pre + ".feed_forward")
+        out += [("dec", l, i, k) for i, k in enumerate(keys)]
+    out += [("enc_norm_a", None, None, "model.encoder.norm.a_2"), ("enc_norm_b", None, None, "model.encoder.norm.b_2"),
+            ("dec_norm_a", None, None, "model.decoder.norm.a_2"), ("dec_norm_b", None, None, "model.decoder.norm.b_2"),
+            ("lut", None, None, "model.tgt_embed.0.lut.weight"), ("pe", None, None, "model.tgt_embed.1.pe"),
+            ("gen_w", None, None, "model.generator.proj.weight"), ("gen_b", None, None, "model.generator.proj.bias")]
+    return out
+
+
+def transformer_weights(tensors, layers, use_bn=0):
+    """Fill a uic_transformer_weights from {reference key: contiguous f32 device tensor}."""
+    w = TransformerWeights()
+    for f, l, i, k in transformer_weight_keys(layers, use_bn):
+        t = tensors[k]
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda, k
+        if l is None:
+            setattr(w, f, t.data_ptr())
+        else:
+            getattr(w, f)[l][i] = t.data_ptr()
+    return w
+
+
+def transformer_d_ff_padded(d_ff):
+    """The reduction length of w_2 (and row count of w_1) in the derived copies: d_ff rounded up to a multiple of 8."""
+    return (int(d_ff) + 7) // 8 * 8
+
+
+def mha_lds_bytes(Sk, d_k):
+    """LDS of one uic_mha_fwd workgroup: K [Sk][d_k + 1], V [Sk][d_k], per wave (4) the probabilities [Sk] and the query [d_k], f32."""
+    return (Sk * (d_k + 1) + Sk * d_k + 4 * (Sk + d_k)) * 4
+
+
 GCN_MAX_LAYERS = 3
 
 
@@ -389,6 +464,20 @@ _SIGS = {
     "uic_cast_to_f32": (C.c_int, [C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
     "uic_transpose": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "uic_dropout_mask": (C.c_int, [C.c_void_p, C.c_size_t, C.c_float, C.c_uint32, C.c_uint32, C.c_size_t, C.c_void_p]),
+    "uic_layernorm_std": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_float,
+                                    C.c_void_p, C.c_int32, C.c_void_p]),
+    "uic_mha_fwd": (C.c_int, [C.c_int32] * 5 + [C.c_void_p, C.c_int32, C.c_int64] * 4 + [C.c_void_p] + [C.c_int32] * 4 + [C.c_void_p]),
+    "uic_transformer_workspace_bytes": (C.c_size_t, [C.POINTER(TransformerDims)]),
+    "uic_transformer_derived_bytes": (C.c_size_t, [C.POINTER(TransformerDims)]),
+    "uic_transformer_refresh_weights": (C.c_int, [C.POINTER(TransformerDims), C.POINTER(TransformerWeights), C.c_void_p, C.c_void_p]),
+    "uic_transformer_encode": (C.c_int, [C.POINTER(TransformerDims), C.POINTER(TransformerWeights)] + [C.c_void_p] * 6),
+    "uic_transformer_forward": (C.c_int, [C.POINTER(TransformerDims), C.POINTER(TransformerWeights)] + [C.c_void_p] * 4 +
+                                [C.c_int32, C.c_int32] + [C.c_void_p] * 3),
+    "uic_transformer_sample": (C.c_int, [C.POINTER(TransformerDims), C.POINTER(TransformerWeights)] + [C.c_void_p] * 3 +
+                               [C.c_int32, C.c_int32, C.c_float, C.c_uint32] + [C.c_void_p] * 4),
+    "uic_transformer_sample_beam": (C.c_int, [C.POINTER(TransformerDims), C.POINTER(TransformerWeights)] + [C.c_void_p] * 3 +
+                                    [C.c_int32] * 4 + [C.c_void_p] * 4),
+    "uic_transformer_beam_done_lists": (C.c_int, [C.POINTER(TransformerDims), C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -104,6 +104,9 @@ class Trainer(object):
         self.i2t_model = models.setup(opt) if getattr(opt, 'caption_model', None) else None
         self.dp_i2t_model = self.i2t_model
         if self.i2t_model is not None:
+            if self.i2t_train_flag and getattr(self.i2t_model, 'eval_only', False):
+                raise NotImplementedError("%s: evaluation and decoding only; training is not built (i2t_train_flag=0 runs Trainer.eval)"
+                                          % type(self.i2t_model).__name__)
             self.i2t_model.train(bool(self.i2t_train_flag))
         self.nmt_model = None
         self.i2t_train_loss = 0.0
