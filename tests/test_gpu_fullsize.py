@@ -4,7 +4,7 @@ the norm of every gradient tensor and three gradient tensors entry by entry -- a
 (csrc/rnn_persist.hip: the decode loop, csrc/rnn_bwd_persist.hip: its BPTT) against the per-step launch chains they replace,
 under both of their exchange protocols.
 The step that bench.py times -- the list of live positions made on the device, training-mode dropout 0.5, and in bf16 the
-persistent kernel's own store of the live hdrop rows into the compact logit operand (Step::fused_gather, csrc/topdown.hip) -- is
+persistent kernel's own store of the live hdrop rows into the compact logit operand (Step::fused_gather, csrc/topdown_step.hip) -- is
 compared with the oracle here as well: test_configs1_full_size_step_over_live_positions_vs_oracle and
 test_full_size_benchmark_dropout_step_vs_oracle (tests/test_gpu_live_persist.py holds the edges at 512 hidden units).
 Tolerances (north_star): log-probs 1e-3 (f32) / 1e-2 (bf16)."""

@@ -1,6 +1,6 @@
 """The step over the live positions at 512 hidden units -- where the persistent recurrence kernel runs (uic_rnn_persist_eligible:
 H == A == 512) and, in bf16 with the list made on the device, stores every live hdrop row into the compact logit operand itself
-(Step::fused_gather, csrc/topdown.hip; rnn_persist.hip: live_inv / hdrop_live) -- against the CPU oracle, with training-mode
+(Step::fused_gather, csrc/topdown_step.hip; rnn_persist.hip: live_inv / hdrop_live) -- against the CPU oracle, with training-mode
 dropout 0.5 (the oracle is fed the kernels' own masks), at the row counts and masks where that store, the list and the
 captions' lengths (cap_len) can go wrong: a handful of rows, ragged 16-row tiles, two launches of <= 640 rows, more positions
 than the list kernel's single round trip, early breaks, holes, empty decode steps, fractional weights, dead rows.  And the

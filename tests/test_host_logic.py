@@ -201,8 +201,9 @@ def test_weight_gradient_dispatch_keeps_no_thread_state():
     assert _mutable_globals("namespace { int a = 0; thread_local int b; const int c = 1; constexpr int d = 2; std::mutex m; "
                             "struct S { int x; }; S s[4]; int f(int x) { return x; } int g(int); }") == ["a", "b", "m", "s"]
     csrc = os.path.join(ROOT, "unpaired_image_captioning_amd", "csrc")
-    allowed = {"topdown.hip": ["g_side", "g_side_mutex"]}
-    for f in ("uic_host.h", "gemm_tn.hip", "gemm_tn_pp.hip", "topdown.hip"):
+    allowed = {"topdown_features.hip": ["g_side", "g_side_mutex"]}
+    for f in ("uic_host.h", "wgrad.hip", "gemm_tn.hip", "gemm_tn_pp.hip", "topdown_internal.h", "topdown_layout.hip",
+              "topdown_features.hip", "topdown_step.hip", "topdown_train.hip", "topdown_decode.hip"):
         src = open(os.path.join(csrc, f)).read()
         assert not re.search(r"\bthread_local\b", re.sub(r"//[^\n]*", "", src)), f
         assert _mutable_globals(src) == allowed.get(f, []), f

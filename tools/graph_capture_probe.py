@@ -3,7 +3,7 @@
 capture works"; VERDICT round 4: untested.)  RESULT, round 5 (ROCm 7.2, MI355X): NO -- the multi-stream capture is accepted
 launch by launch (an un-joined side stream is reported as hipErrorStreamCaptureUnjoined, which is how the ordering of the
 gradient-group flag kernels was found and fixed), but hipStreamEndCapture then dies with a segmentation fault inside the
-runtime.  csrc/topdown.hip says so; this probe is the evidence and the way to re-check on a newer ROCm.  Captures uic_topdown_refresh_weights + uic_topdown_xe_train_step -- the caller's stream
+runtime.  csrc/topdown_train.hip says so; this probe is the evidence and the way to re-check on a newer ROCm.  Captures uic_topdown_refresh_weights + uic_topdown_xe_train_step -- the caller's stream
 plus the library's four side streams, forked and joined by events -- in relaxed mode, replays the graph and compares every
 gradient bit for bit with the eager step.    gpurun -- python tools/graph_capture_probe.py [--full]"""
 import ctypes as C

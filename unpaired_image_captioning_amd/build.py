@@ -4,13 +4,14 @@
 
 hipcc cross-compiles without a GPU, so this also is the "does it build" check.
 """
+import glob
 import os
 import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["api.hip", "gemm.hip", "gemm_pp.hip", "gemm_tn.hip", "gemm_tn_pp.hip", "attention.hip", "rnn_persist.hip", "rnn_bwd_persist.hip", "bptt_fused.hip", "pointwise.hip", "embedding.hip", "lstm_cell.hip", "adam.hip", "sampling.hip", "live_rows.hip", "criterion.hip", "batchnorm.hip", "beam.hip", "ensemble.hip", "topdown.hip", "fcmodel.hip", "nmt.hip", "nmt_persist.hip", "cider.hip", "loader.hip", "loader_io.hip", "comm.hip", "discriminator.hip", "gcn.hip", "transformer.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_pp.hip", "gemm_tn.hip", "gemm_tn_pp.hip", "attention.hip", "rnn_persist.hip", "rnn_bwd_persist.hip", "bptt_fused.hip", "pointwise.hip", "embedding.hip", "lstm_cell.hip", "adam.hip", "sampling.hip", "live_rows.hip", "criterion.hip", "batchnorm.hip", "beam.hip", "ensemble.hip", "wgrad.hip", "topdown_layout.hip", "topdown_features.hip", "topdown_step.hip", "topdown_train.hip", "topdown_decode.hip", "fcmodel.hip", "nmt.hip", "nmt_persist.hip", "cider.hip", "loader.hip", "loader_io.hip", "comm.hip", "discriminator.hip", "gcn.hip", "transformer.hip"]
 LIB = os.path.join(HERE, "libuic_hip.so")
 
 
@@ -20,7 +21,7 @@ def _newest(paths):
 
 def build(force: bool = False, verbose: bool = True) -> str:
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
-    deps = srcs + [os.path.join(CSRC, "uic_common.h"), os.path.join(CSRC, "uic_host.h"), os.path.join(CSRC, "rnn_persist_common.h"), os.path.join(HERE, "..", "include", "uic_hip.h")]
+    deps = srcs + sorted(glob.glob(os.path.join(CSRC, "*.h"))) + [os.path.join(HERE, "..", "include", "uic_hip.h")]
     if not force and os.path.exists(LIB) and os.path.getmtime(LIB) >= _newest(deps):
         return LIB
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

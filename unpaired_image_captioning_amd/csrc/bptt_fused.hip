@@ -1,4 +1,4 @@
-// One launch for two links of the BPTT chain (Step::bwd_step, topdown.hip): the `h2att` input-gradient GEMM
+// One launch for two links of the BPTT chain (Step::bwd_step, topdown_step.hip): the `h2att` input-gradient GEMM
 //     d h_att (+)= d att_h W_h2att                     (backward of P/models/AttModel.py:543)
 // and the att_lstm cell backward that consumes it (backward of nn.LSTMCell, :434), whose other d h sources are the split-K
 // partial slabs of the step's d x2 GEMM and of the previous step's d x1 GEMM.  The BPTT loop is a chain of dependent launches

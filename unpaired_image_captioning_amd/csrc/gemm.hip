@@ -882,7 +882,7 @@ __global__ void splitk_reduce_vec_kernel(const float* __restrict__ slab, int spl
   }
 }
 // the same sum with the output rows placed by a list: row r < map_rows of the slab goes to row map[r] of C (entries outside
-// [0, map_limit) -- a list's -1 padding -- and rows >= map_rows are dropped).  The live-position logit layer's d hdrop (topdown.hip).
+// [0, map_limit) -- a list's -1 padding -- and rows >= map_rows are dropped).  The live-position logit layer's d hdrop (topdown_step.hip).
 __global__ void splitk_reduce_rows_kernel(const float* __restrict__ slab, int splitk, int M, int N, const int* __restrict__ map, int map_rows,
                                           int map_limit, float* __restrict__ C, int ldc) {
   const int c = (blockIdx.x * blockDim.x + threadIdx.x) * 4;

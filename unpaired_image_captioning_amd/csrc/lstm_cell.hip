@@ -48,7 +48,7 @@ __global__ void lstm_bwd_kernel(const UicLstmBwdParams p) {
 // The same for H % 4 == 0 and 16-byte aligned rows: FOUR hidden units per lane, one 16-byte (f32) / 8-byte (bf16) access per
 // tensor and gate instead of four scalar ones -- the kernel sits in the BPTT chain 34 times per step and is made of memory
 // latency and instruction issue, not of bytes (captioner step 3.775 -> 3.757 ms over six alternations).  Same formulas per element.
-// SIMPLE: dh0 and c_prev present, dh1 / dh2 absent -- the two calls of the split BPTT chain (topdown.hip); then no load has an
+// SIMPLE: dh0 and c_prev present, dh1 / dh2 absent -- the two calls of the split BPTT chain (topdown_step.hip); then no load has an
 // optional address at all, only the slab stand-ins below.
 template <typename T, bool SIMPLE>
 __global__ __launch_bounds__(NT) void lstm_bwd_vec4_kernel(const UicLstmBwdParams p) {

@@ -1,7 +1,7 @@
 // Persistent, step-fused BPTT of the TopDown captioner's recurrence for gfx950 (MI355X): ONE launch runs the backward of
 // decode steps [t_lo, t_hi) of AttModel._forward's loop body (P/models/AttModel.py:129-154 -> TopDownCore.forward
 // :430-446 -> Attention.forward :538-558), latest step first, instead of six dependent launches per step
-// (Step::bwd_step in topdown.hip: lstm_bwd, d x2 GEMM, attention backward, h2att GEMM, lstm_bwd, d x1 GEMM).
+// (Step::bwd_step in topdown_step.hip: lstm_bwd, d x2 GEMM, attention backward, h2att GEMM, lstm_bwd, d x1 GEMM).
 //
 // Decomposition = the forward kernel's (rnn_persist.hip): caption rows are independent, so the chip is cut into 8 row
 // groups (one per XCD where the placement allows, else the SAFE protocol), and inside a group workgroup `rank` owns 16

@@ -300,7 +300,7 @@ struct UicGemmTnParams {
 struct UicSlabDest { float* C; int ldc, col0, ncols; };
 int uic_splitk_reduce_multi_launch(const float* slab, int splitk, int M, int N, const UicSlabDest* dst, int nd, int accumulate, hipStream_t s);
 bool uic_gemm_tn_eligible(const UicGemmTnParams& p);
-// Where a weight-gradient launch runs (wgrad_multi / wgrad_tn / wgrad_group of uic_host.h, uic_gemm_tn_launch): it decides the
+// Where a weight-gradient launch runs (wgrad_multi / wgrad_tn / wgrad_group of wgrad.hip, uic_gemm_tn_launch): it decides the
 // kernel and the split over K, so the caller passes it with every call.
 enum UicWgPlace {
   UIC_WG_ALONE = 0,          // alone on the chip: split over K until ~one workgroup per CU; such grids take the 4-stage TN kernel
@@ -316,6 +316,28 @@ int uic_gemm_tnpp_launch(const UicGemmTnParams& p, hipStream_t s);
 #define UIC_TN_FORCE_128 0x100     // the 128 x 128 kernel (gemm_tn.hip)
 #define UIC_TN_FORCE_256 0x200     // the 256 x 256 ping-pong kernel (gemm_tn_pp.hip); an ineligible problem is an error
 #define UIC_TN_SPLITK(n) (((n) & 0xff) << 16)   // K slices (0: the dispatcher's choice)
+
+// ---------------------------------------------------------------- weight-gradient dispatch (wgrad.hip)
+// Weight gradient(s) C_i = left[lrows, K] * right[cols_i, K]^T for one or several destinations that share `left`
+// (right operands stacked row-wise in `right`).  Long-K, few-tile problems run split-K over workgroups on the
+// LDS-DMA GEMM with deterministic slab reduction; anything else falls back to one direct GEMM per destination.
+struct WDest { float* C; int ldc; int col0; int ncols; };
+// rows: optional (one destination, no accumulate): the split-K path stores output row r < rows->n at row rows->map[r] of rows->C
+// instead of dst (entries outside [0, rows->limit) dropped) and sets rows->used; the direct path ignores it and writes dst
+struct WRows { const int* map; int n; int limit; float* C; int ldc; bool used; };
+int wgrad_multi(float* slab, size_t slab_bytes, int dt, const void* left, int lrows, const void* right, int rrows, int K,
+                const WDest* dst, int nd, hipStream_t s, bool accumulate = false, WRows* rows = nullptr, UicWgPlace at = UIC_WG_ALONE);
+// The same weight gradients WITHOUT transposed copies (bf16, gfx950 transposing LDS reads, gemm_tn.hip / gemm_tn_pp.hip):
+// C_i = A[K, lrows]^T * [B_0 | B_1 | ...][K, cols].  Returns UIC_OK with *done = false when the shape is not eligible (the
+// caller then transposes and uses wgrad_multi).
+// how: UIC_TN_FORCE_* | UIC_TN_SPLITK(n) for measurements and tests (0: the dispatcher's choice).
+int wgrad_tn(float* slab, size_t slab_bytes, int dt, const void* A, int lda, int lrows, const UicGemmTnSeg* segs, int nseg,
+             int K, const WDest* dst, int nd, hipStream_t s, bool accumulate, bool* done, int how = 0, UicWgPlace at = UIC_WG_ALONE);
+// One group of weight gradients sharing the left operand:  C_i = A[rows, lrows]^T * [B_0 | B_1 | ...][rows, cols].
+// bf16 on eligible shapes: gemm_tn.hip reads both operands as they lie (transposing LDS reads).  Otherwise (f32 parity path,
+// odd sizes): transposed copies into tA [lrows, rows^8] / tB [cols, rows^8] and the NT kernels (wgrad_multi).
+int wgrad_group(float* slab, size_t slab_bytes, int dt, const void* A, int lda, int lrows, const UicGemmTnSeg* segs, int nseg,
+                int rows, const WDest* dst, int nd, hipStream_t s, bool accumulate, void* tA, void* tB, UicWgPlace at = UIC_WG_ALONE);
 
 // ---------------------------------------------------------------- attention (attention.hip)
 struct UicAttnParams {
@@ -359,7 +381,7 @@ int uic_attention_bwd_accum_launch(const UicAttnAccumParams& p, hipStream_t s);
 
 // ---------------------------------------------------------------- persistent recurrence (rnn_persist.hip)
 // Decode steps [t0, t1) of the TopDown recurrence (P/models/AttModel.py:129-154, :430-446, :538-558) in ONE launch.
-// All state / activation buffers are the time-major workspace slabs of topdown.hip (step stride N*H etc.).
+// All state / activation buffers are the time-major workspace slabs of topdown_layout.hip (step stride N*H etc.).
 struct UicRnnFwdParams {
   int dtype, N, R, t0, t1;
   int row0, Nrows;                   // filled by the launcher (slabs of <= 640 caption rows)
@@ -430,7 +452,7 @@ int uic_rnn_fwd_persist_launch(const UicRnnFwdParams& p, hipStream_t s);
 // BPTT of decode steps [t_lo, t_hi) of the same recurrence (latest step first) in ONE launch (rnn_bwd_persist.hip; bf16):
 // per step lang_lstm cell backward, d[att_res | h_att | h_lang_prev] = dG2 W2, attention backward (scores, softmax,
 // d att_h), d h_att += d att_h W_h2att, att_lstm cell backward, d[h_lang_prev | h_att_prev] = dG1 W1rec -- the six dependent
-// launches per step of Step::bwd_step (topdown.hip).  Reads what the forward pass saved, writes what the weight-gradient
+// launches per step of Step::bwd_step (topdown_step.hip).  Reads what the forward pass saved, writes what the weight-gradient
 // GEMMs and the deferred attention accumulation read afterwards (dg1_all, dg2_all, datth_all, de_all, the d ctx columns of
 // dx2_all); the gradients carried from step to step enter and leave through dc_att, dc_lang, dx1 and the h_lang columns of
 // dx2_all[t_hi] / dx2_all[t_lo] -- the buffers of the launch chain's UNSPLIT form only: once the chain splits its d x GEMMs
