@@ -646,7 +646,58 @@ int uic_h2att_cell_bwd(int32_t dtype, int32_t N, int32_t H, int32_t A, const voi
                        const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
                        float* dc, const void* gates, const float* c_prev, const float* c, void* dgates, void* stream);
 
-/* Attention.forward after h2att (P/models/AttModel.py:544-556). */
+/* Attention.forward after h2att (P/models/AttModel.py:544-556) and its backward, split into the part inside the BPTT loop (step) and
+ * the sums over the decode steps behind it (accum); csrc/attention.hip.  p_att [N,R,A], att [N,R,H], ctx and d_att_h in `dtype`
+ * (UIC_DTYPE_F32 / UIC_DTYPE_BF16), everything else f32.  A and H multiples of 4 (f32) / 8 (bf16) = vec; R, A, H > 0.
+ *   forward:  e_r = w_alpha . tanh(p_att[r] + att_h) + b_alpha;  alpha = softmax_r(e), with a mask alpha_r mask_r / sum_j alpha_j mask_j;
+ *             ctx = sum_r alpha_r att[r].   alpha [N,R] and ctx (row n at ctx + n ld_ctx, ld_ctx >= H) are written, nothing else.
+ *   step:     d ctx = dctx + sum_{1 <= z < nslab} slab z, in that order (slab z at dctx + z slab_stride; row n at + n lddctx,
+ *             lddctx >= H; nslab 0 or 1: dctx alone), left in dctx_sum (optional, row n at + n ld_dctx_sum >= H);
+ *             d alpha_r = d ctx . att[r];  de_r = alpha_r (d alpha_r - sum_j alpha_j d alpha_j)   [N,R] out;
+ *             d_att_h[a] = w_a sum_r de_r (1 - tanh^2(p_att[r,a] + att_h[a]))                     [N,A] out.
+ *             row_len (optional, [N] int32) with step >= 0: a row with step >= row_len[n] gets EXACT ZEROS in de, d_att_h and
+ *             dctx_sum and none of its operands is read, whichever kernel runs.
+ *   accum:    d_att[n,r,:] = sum_{t < TS} alpha_t[r] dctx_t;  d_p_att[n,r,a] = w_a sum_{t < TS} de_t[r] (1 - tanh^2(p_att[r,a] + att_h_t[a]));
+ *             d_walpha_part[n, a] = sum_{t < TS, r} de_t[r] tanh(.), d_walpha_part[n, A] = sum de;  TS = T, with row_len (optional)
+ *             min(T, max(row_len[n], 0)): the steps behind a caption's end are not read.  att_h_all [T,N,A], alpha_all / de_all [T,N,R]
+ *             contiguous; d ctx of (t, n) at dctx_all + t dctx_step_stride + n lddctx, lddctx >= H.  T > 0.
+ * Kernels (*kernel_id, host, optional, is set by every accepted call):
+ *   forward / step:  UIC_ATTN_FAST when R <= 36, A / vec <= 64, H / vec <= 64 and att_h and w_alpha are 16-byte aligned -- for the
+ *     step also lddctx % 4 == 0, dctx 16-byte aligned, slab_stride % 4 == 0 when nslab > 1, and dctx_sum absent or 16-byte aligned
+ *     with ld_dctx_sum % 4 == 0;  UIC_ATTN_FAST_FULL when moreover A == H == 64 vec;  UIC_ATTN_GENERIC otherwise: it reads those
+ *     operands one word at a time.
+ *   accum:  bit UIC_ATTN_ACCUM_P1_R6 (d_att by attn_bwd_accum_p1_kernel) when lddctx % 4 == 0, dctx_step_stride % 4 == 0 and dctx_all
+ *     is 16-byte aligned;  bit UIC_ATTN_ACCUM_P2_R6 (d_p_att and d_walpha_part by attn_bwd_accum_p2_bf16_kernel) for bf16 with
+ *     att_h_all and w_alpha 16-byte aligned and p_att, d_p_att 8-byte aligned;  a clear bit: attn_bwd_accum_kernel<T, PART>, which
+ *     reads att_h_all, w_alpha and dctx_all one word at a time.
+ * REFUSED (non-zero return, uic_last_error_string names the operator, NOTHING is launched and no output is touched): a dtype other
+ * than the two, sizes out of range, A or H no multiple of vec, a null pointer among the required operands, a leading dimension
+ * below its width, nslab < 0, step < 0 with a row_len;  p_att or att not 16-byte aligned (forward, step: every kernel reads them
+ * 16 bytes at a time);  d_att not 16-byte aligned, and p_att / d_p_att not 16-byte aligned unless the bf16 kernel takes the call
+ * (accum);  more than 160 KB of LDS (forward: 4 (2A + 4R + 4 + 4H) B, step: 4 (6A + H + 5 (R rounded up to 4)) B, accum: 4 T (H + R) or
+ * 4 (T (A + R) + 5A) B with R rounded up to 4).  Up to 160 KB a call runs: the launchers ask for what exceeds a launch's 64 KB.
+ * N == 0 is a successful no-op.  uic_attention_fwd / _bwd_step / _bwd_accum are the same calls with ld_mask = R, ld_ctx = lddctx = H,
+ * dctx_step_stride = N H, no slabs, no dctx_sum, no row_len, no kernel_id.
+ * tests/test_gpu_attention.py holds every kernel against float64, element by element, on both sides of each condition above;
+ * tests/attention_cases.py restates the choice and tests/test_attention_cases_host.py checks the cases and the bound on the CPU. */
+#define UIC_ATTN_GENERIC 0       /* attn_fwd_kernel<T> / attn_bwd_step_kernel<T> */
+#define UIC_ATTN_FAST 1          /* attn_fwd_fast_kernel<T, NW, false> / attn_bwd_step_fast_kernel<T, false> */
+#define UIC_ATTN_FAST_FULL 2     /* attn_fwd_fast_kernel<T, NW, true> / attn_bwd_step_fast_kernel<T, true> */
+#define UIC_ATTN_ACCUM_P1_R6 1   /* bit: attn_bwd_accum_p1_kernel, else attn_bwd_accum_kernel<T, 1> */
+#define UIC_ATTN_ACCUM_P2_R6 2   /* bit: attn_bwd_accum_p2_bf16_kernel, else attn_bwd_accum_kernel<T, 2> */
+int uic_attention_fwd_strided(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,
+                              const void* att, const float* w_alpha, const float* b_alpha, const float* mask, int32_t ld_mask,
+                              float* alpha, void* ctx, int32_t ld_ctx, int32_t* kernel_id, void* stream);
+int uic_attention_bwd_step_sources(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h,
+                                   const void* p_att, const void* att, const float* w_alpha, const float* alpha,
+                                   const float* dctx, int32_t lddctx, int32_t nslab, size_t slab_stride,
+                                   float* dctx_sum, int32_t ld_dctx_sum, const int32_t* row_len, int32_t step,
+                                   float* de, void* d_att_h, int32_t* kernel_id, void* stream);
+int uic_attention_bwd_accum_strided(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, int32_t T,
+                                    const float* att_h_all, const float* alpha_all, const float* de_all, const float* dctx_all,
+                                    int32_t lddctx, size_t dctx_step_stride, const int32_t* row_len,
+                                    const void* p_att, const float* w_alpha, float* d_att, void* d_p_att, float* d_walpha_part,
+                                    int32_t* kernel_id, void* stream);
 int uic_attention_fwd(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,
                       const void* att, const float* w_alpha, const float* b_alpha, const float* mask, float* alpha,
                       void* ctx, void* stream);

@@ -31,6 +31,8 @@ STEP_MARKS = 11          # UIC_STEP_MARKS
 
 XE_GENERIC, XE_LDS, XE_REG, XE_REG_WIDE, XE_BIG = 0, 1, 2, 3, 4     # UIC_XE_*: the kernel uic_xe_criterion launched
 LSTM_BWD_SCALAR, LSTM_BWD_VEC4, LSTM_BWD_VEC4_SIMPLE = 0, 1, 2      # UIC_LSTM_BWD_*: the kernel uic_lstm_cell_bwd_sources launched
+ATTN_GENERIC, ATTN_FAST, ATTN_FAST_FULL = 0, 1, 2                  # UIC_ATTN_*: the forward / step kernel of uic_attention_*_strided / _sources
+ATTN_ACCUM_P1_R6, ATTN_ACCUM_P2_R6 = 1, 2                           # UIC_ATTN_ACCUM_*: bits of uic_attention_bwd_accum_strided's kernel_id
 XE_KERNEL_NAMES = ("xe_kernel", "xe_lds_kernel", "xe_reg_kernel", "xe_reg_wide_kernel", "xe_big_kernel")
 
 MAX_LOGIT_LAYERS = 4
@@ -424,6 +426,13 @@ _SIGS = {
     "uic_attention_fwd": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 9),
     "uic_attention_bwd_step": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 9),
     "uic_attention_bwd_accum": (C.c_int, [C.c_int32] * 6 + [C.c_void_p] * 10),
+    "uic_attention_fwd_strided": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 6 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                                                               C.POINTER(C.c_int32), C.c_void_p]),
+    "uic_attention_bwd_step_sources": (C.c_int, [C.c_int32] * 5 + [C.c_void_p] * 5 + [C.c_void_p, C.c_int32, C.c_int32, C.c_size_t] +
+                                       [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32),
+                                        C.c_void_p]),
+    "uic_attention_bwd_accum_strided": (C.c_int, [C.c_int32] * 6 + [C.c_void_p] * 4 + [C.c_int32, C.c_size_t] + [C.c_void_p] * 6 +
+                                        [C.POINTER(C.c_int32), C.c_void_p]),
     "uic_optim_states": (C.c_int, [C.c_int32]),
     "uic_optim_step": (C.c_int, [C.POINTER(OptimConfig)] + [C.c_void_p] * 4 + [C.c_size_t, C.c_void_p]),
     "uic_optim_step_ranges": (C.c_int, [C.POINTER(OptimConfig)] + [C.c_void_p] * 4 + [C.c_int32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64),

@@ -201,35 +201,57 @@ int uic_h2att_cell_bwd(int32_t dtype, int32_t N, int32_t H, int32_t A, const voi
   return uic_h2att_cell_bwd_launch(p, (hipStream_t)stream);
 }
 
-int uic_attention_fwd(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,
-                      const void* att, const float* w_alpha, const float* b_alpha, const float* mask, float* alpha,
-                      void* ctx, void* stream) {
+int uic_attention_fwd_strided(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,
+                              const void* att, const float* w_alpha, const float* b_alpha, const float* mask, int32_t ld_mask,
+                              float* alpha, void* ctx, int32_t ld_ctx, int32_t* kernel_id, void* stream) {
   UicAttnParams a;
   memset(&a, 0, sizeof(a));
   a.dtype = dtype; a.N = N; a.R = R; a.A = A; a.H = H; a.att_h = att_h; a.p_att = p_att; a.att = att;
-  a.w_alpha = w_alpha; a.b_alpha = b_alpha; a.mask = mask; a.ldmask = R; a.alpha = alpha; a.ctx = ctx; a.ldctx = H;
-  return uic_attention_fwd_launch(a, (hipStream_t)stream);
+  a.w_alpha = w_alpha; a.b_alpha = b_alpha; a.mask = mask; a.ldmask = ld_mask; a.alpha = alpha; a.ctx = ctx; a.ldctx = ld_ctx;
+  return uic_attention_fwd_launch(a, (hipStream_t)stream, kernel_id);
+}
+int uic_attention_fwd(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,
+                      const void* att, const float* w_alpha, const float* b_alpha, const float* mask, float* alpha,
+                      void* ctx, void* stream) {
+  return uic_attention_fwd_strided(dtype, N, R, A, H, att_h, p_att, att, w_alpha, b_alpha, mask, R, alpha, ctx, H, nullptr, stream);
+}
+int uic_attention_bwd_step_sources(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h,
+                                   const void* p_att, const void* att, const float* w_alpha, const float* alpha,
+                                   const float* dctx, int32_t lddctx, int32_t nslab, size_t slab_stride,
+                                   float* dctx_sum, int32_t ld_dctx_sum, const int32_t* row_len, int32_t step,
+                                   float* de, void* d_att_h, int32_t* kernel_id, void* stream) {
+  UicAttnParams a;
+  memset(&a, 0, sizeof(a));
+  a.dtype = dtype; a.N = N; a.R = R; a.A = A; a.H = H; a.att_h = att_h; a.p_att = p_att; a.att = att;
+  a.w_alpha = w_alpha; a.alpha = (float*)alpha; a.dctx = dctx; a.lddctx = lddctx; a.dctx_nslab = nslab; a.dctx_slab_stride = slab_stride;
+  a.dctx_sum = dctx_sum; a.ld_dctx_sum = ld_dctx_sum; a.row_len = row_len; a.step = step; a.de = de; a.d_att_h = d_att_h;
+  return uic_attention_bwd_step_launch(a, (hipStream_t)stream, kernel_id);
 }
 int uic_attention_bwd_step(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h,
                            const void* p_att, const void* att, const float* w_alpha, const float* alpha,
                            const float* dctx, float* de, void* d_att_h, void* stream) {
-  UicAttnParams a;
+  return uic_attention_bwd_step_sources(dtype, N, R, A, H, att_h, p_att, att, w_alpha, alpha, dctx, H, 0, 0, nullptr, 0, nullptr, 0,
+                                        de, d_att_h, nullptr, stream);
+}
+int uic_attention_bwd_accum_strided(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, int32_t T,
+                                    const float* att_h_all, const float* alpha_all, const float* de_all, const float* dctx_all,
+                                    int32_t lddctx, size_t dctx_step_stride, const int32_t* row_len,
+                                    const void* p_att, const float* w_alpha, float* d_att, void* d_p_att, float* d_walpha_part,
+                                    int32_t* kernel_id, void* stream) {
+  UicAttnAccumParams a;
   memset(&a, 0, sizeof(a));
-  a.dtype = dtype; a.N = N; a.R = R; a.A = A; a.H = H; a.att_h = att_h; a.p_att = p_att; a.att = att;
-  a.w_alpha = w_alpha; a.alpha = (float*)alpha; a.dctx = dctx; a.lddctx = H; a.de = de; a.d_att_h = d_att_h;
-  return uic_attention_bwd_step_launch(a, (hipStream_t)stream);
+  a.dtype = dtype; a.N = N; a.R = R; a.A = A; a.H = H; a.T = T;
+  a.att_h_all = att_h_all; a.alpha_all = alpha_all; a.de_all = de_all;
+  a.dctx_all = dctx_all; a.lddctx = lddctx; a.dctx_step_stride = dctx_step_stride; a.row_len = row_len;
+  a.p_att = p_att; a.w_alpha = w_alpha; a.d_att = d_att; a.d_p_att = d_p_att; a.d_walpha_part = d_walpha_part;
+  return uic_attention_bwd_accum_launch(a, (hipStream_t)stream, kernel_id);
 }
 int uic_attention_bwd_accum(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, int32_t T,
                             const float* att_h_all, const float* alpha_all, const float* de_all, const float* dctx_all,
                             const void* p_att, const float* w_alpha, float* d_att, void* d_p_att, float* d_walpha_part,
                             void* stream) {
-  UicAttnAccumParams a;
-  memset(&a, 0, sizeof(a));
-  a.dtype = dtype; a.N = N; a.R = R; a.A = A; a.H = H; a.T = T;
-  a.att_h_all = att_h_all; a.alpha_all = alpha_all; a.de_all = de_all;
-  a.dctx_all = dctx_all; a.lddctx = H; a.dctx_step_stride = (size_t)N * H;
-  a.p_att = p_att; a.w_alpha = w_alpha; a.d_att = d_att; a.d_p_att = d_p_att; a.d_walpha_part = d_walpha_part;
-  return uic_attention_bwd_accum_launch(a, (hipStream_t)stream);
+  return uic_attention_bwd_accum_strided(dtype, N, R, A, H, T, att_h_all, alpha_all, de_all, dctx_all, H, (size_t)(N > 0 ? N : 0) * H,
+                                         nullptr, p_att, w_alpha, d_att, d_p_att, d_walpha_part, nullptr, stream);
 }
 
 int uic_optim_states(int32_t method) { return uic_optim_state_count(method); }

@@ -13,6 +13,7 @@
 //                                  d p_att[n,r,a] = sum_t de_t[r] w_a (1 - tanh^2(p_att + att_h_t))
 //     one pass, no read-modify-write of [N,R,*] accumulators per decode step.
 #include "uic_common.h"
+#include "../../include/uic_hip.h"
 
 namespace {
 
@@ -139,6 +140,15 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_step_kernel(const UicAttnPa
   float* s_red = s_da + Rp;
   const int n = blockIdx.x;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (p.row_len && p.step >= p.row_len[n]) {
+    // a caption that ended before this decode step: exact zeros, no operand read (the same exit as attn_bwd_step_fast_kernel, so
+    // that what such a row gets does not depend on which kernel the launcher picks)
+    if (p.dctx_sum) for (int h = tid; h < H; h += NTHREADS) p.dctx_sum[(size_t)n * p.ld_dctx_sum + h] = 0.f;
+    for (int r = tid; r < R; r += NTHREADS) p.de[(size_t)n * R + r] = 0.f;
+    T* out0 = (T*)p.d_att_h + (size_t)n * A;
+    for (int a = tid; a < A; a += NTHREADS) out0[a] = uic_from_f<T>(0.f);
+    return;
+  }
 
   for (int a = tid; a < A; a += NTHREADS) {
     s_atth[a] = p.att_h[(size_t)n * A + a];
@@ -453,9 +463,17 @@ __global__ __launch_bounds__(NTHREADS) void attn_bwd_step_fast_kernel(const UicA
     out[a] = uic_from_f<T>(s_red[a] + s_red[A + a] + s_red[2 * A + a] + s_red[3 * A + a]);
 }
 
-inline bool fast_ok(const UicAttnParams& p) {
+inline bool al16(const void* q) { return ((uintptr_t)q & 15) == 0; }
+// The fast kernels read att_h and w_alpha 16 bytes at a time (the step kernel d ctx and its slabs too, and it stores dctx_sum
+// that way); the generic kernels touch those operands one word at a time, so a call that fails a condition here is theirs.
+inline bool fast_ok(const UicAttnParams& p, bool step) {
   const int vec = p.dtype == UIC_BF16 ? 8 : 4;
-  return p.R <= UB * NWAVES && p.A / vec <= 64 && p.H / vec <= 64 && (p.lddctx % 4 == 0);
+  bool ok = p.R <= UB * NWAVES && p.A / vec <= 64 && p.H / vec <= 64 && al16(p.att_h) && al16(p.w_alpha);
+  if (step) {
+    ok = ok && p.lddctx % 4 == 0 && al16(p.dctx) && (p.dctx_nslab <= 1 || p.dctx_slab_stride % 4 == 0);
+    ok = ok && (!p.dctx_sum || (al16(p.dctx_sum) && p.ld_dctx_sum % 4 == 0));
+  }
+  return ok;
 }
 
 // PART 1: d att' only (stages alpha, dctx);  PART 2: d p_att and d w_alpha only (stages att_h, de).  Two launches of
@@ -465,10 +483,12 @@ template <typename T, int PART>
 __global__ __launch_bounds__(512) void attn_bwd_accum_kernel(const UicAttnAccumParams p) {
   constexpr int VEC = uic_vec<T>::N;
   extern __shared__ __attribute__((aligned(16))) float sm[];
-  const int A = p.A, H = p.H, R = p.R, TS = p.T, N = p.N;
+  const int A = p.A, H = p.H, R = p.R, N = p.N;
   const int Rp = (R + 3) & ~3;
   const int nthreads = blockDim.x, nw = blockDim.x >> 6;
   const int n = blockIdx.x;
+  // (the steps behind the caption's end are left out, as in the round-6 kernels; no step at all: the loops below write zeros)
+  const int TS = p.row_len ? max(0, min(p.T, p.row_len[n])) : p.T;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
 
   if constexpr (PART == 1) {
@@ -842,31 +862,44 @@ __global__ __launch_bounds__(256) void attn_bwd_accum_p2_bf16_kernel(const UicAt
   if (tid == 0 && blockIdx.y == 0) part[A] = tot;
 }
 
-int check_common(int dtype, int N, int R, int A, int H) {
+int check_common(const char* who, int dtype, int N, int R, int A, int H) {
   const int vec = dtype == UIC_BF16 ? 8 : 4;
-  UIC_REQUIRE(dtype == UIC_F32 || dtype == UIC_BF16, "attention: bad dtype %d", dtype);
-  UIC_REQUIRE(N >= 0 && R > 0 && A > 0 && H > 0, "attention: bad sizes N=%d R=%d A=%d H=%d", N, R, A, H);
-  UIC_REQUIRE(A % vec == 0 && H % vec == 0, "attention: A=%d and H=%d must be multiples of %d", A, H, vec);
+  UIC_REQUIRE(dtype == UIC_F32 || dtype == UIC_BF16, "%s: bad dtype %d", who, dtype);
+  UIC_REQUIRE(N >= 0 && R > 0 && A > 0 && H > 0, "%s: bad sizes N=%d R=%d A=%d H=%d", who, N, R, A, H);
+  UIC_REQUIRE(A % vec == 0 && H % vec == 0, "%s: A=%d and H=%d must be multiples of %d", who, A, H, vec);
+  return UIC_OK;
+}
+
+// (more than 64 KB of dynamic LDS has to be asked for per kernel, up to the 160 KB of a CU)
+template <typename K>
+int launch_attn(K kernel, const UicAttnParams& p, int nthreads, size_t lds, hipStream_t s, const char* what) {
+  if (lds > 64 * 1024)
+    UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds), "hipFuncSetAttribute"));
+  hipLaunchKernelGGL(kernel, dim3(p.N), dim3(nthreads), lds, s, p);
+  UIC_LAUNCH_CHECK(what);
   return UIC_OK;
 }
 
 }  // namespace
 
-int uic_attention_fwd_launch(const UicAttnParams& p, hipStream_t s) {
-  UIC_TRY(check_common(p.dtype, p.N, p.R, p.A, p.H));
+int uic_attention_fwd_launch(const UicAttnParams& p, hipStream_t s, int* kernel_id) {
+  UIC_TRY(check_common("attention_fwd", p.dtype, p.N, p.R, p.A, p.H));
   UIC_REQUIRE(p.att_h && p.p_att && p.att && p.w_alpha && p.alpha && p.ctx, "attention_fwd: null pointer");
-  if (p.N == 0) return UIC_OK;
+  UIC_REQUIRE(p.ldctx >= p.H && (!p.mask || p.ldmask >= p.R), "attention_fwd: ld_ctx=%d < H=%d or ld_mask=%d < R=%d", p.ldctx, p.H, p.ldmask, p.R);
+  UIC_REQUIRE(al16(p.p_att) && al16(p.att), "attention_fwd: p_att and att must be 16-byte aligned (every kernel reads them 16 bytes at a time)");
   const size_t lds = sizeof(float) * (2 * (size_t)p.A + 4 * (size_t)p.R + 4 + NWAVES * (size_t)p.H);
   UIC_REQUIRE(lds <= 160 * 1024, "attention_fwd: needs %zu B of LDS", lds);
-  if (fast_ok(p)) {
+  const int vec = p.dtype == UIC_BF16 ? 8 : 4;
+  const bool fast = fast_ok(p, false), full = fast && p.A == 64 * vec && p.H == 64 * vec;
+  if (kernel_id) *kernel_id = full ? UIC_ATTN_FAST_FULL : fast ? UIC_ATTN_FAST : UIC_ATTN_GENERIC;
+  if (p.N == 0) return UIC_OK;
+  if (fast) {
     // waves per caption row, measured at N = 640 (bf16; 3 alternating passes each): 4 -> 12.1 us cache-resident / 13.5 us
     // HBM-cold, 8 -> 11.8-12.5 / 12.9-13.1, 9 -> 12.3 / 13.1, 6 -> 12.4 / 13.4, 12 -> 11.7 / 12.8-12.9 (3 regions per wave).
     // 12 costs the two-stream training step 0.4 % (a 768-thread workgroup leaves the side stream fewer free slots) and is
     // taken for the steadier, faster kernel.
     const size_t lds8 = sizeof(float) * (4 * (size_t)p.R + 4 + 8 * (size_t)p.H);
     const size_t lds12 = sizeof(float) * (4 * (size_t)p.R + 4 + 12 * (size_t)p.H);
-    const int vec = p.dtype == UIC_BF16 ? 8 : 4;
-    const bool full = p.A == 64 * vec && p.H == 64 * vec;
     if (p.dtype == UIC_BF16) {
       if (full) hipLaunchKernelGGL((attn_fwd_fast_kernel<bf16_t, 12, true>), dim3(p.N), dim3(768), lds12, s, p);
       else hipLaunchKernelGGL((attn_fwd_fast_kernel<bf16_t, 12, false>), dim3(p.N), dim3(768), lds12, s, p);
@@ -874,56 +907,65 @@ int uic_attention_fwd_launch(const UicAttnParams& p, hipStream_t s) {
       if (full) hipLaunchKernelGGL((attn_fwd_fast_kernel<float, 8, true>), dim3(p.N), dim3(512), lds8, s, p);
       else hipLaunchKernelGGL((attn_fwd_fast_kernel<float, 8, false>), dim3(p.N), dim3(512), lds8, s, p);
     }
-  } else if (p.dtype == UIC_BF16)
-    hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, dim3(p.N), dim3(NTHREADS), lds, s, p);
-  else
-    hipLaunchKernelGGL(attn_fwd_kernel<float>, dim3(p.N), dim3(NTHREADS), lds, s, p);
-  UIC_LAUNCH_CHECK("attn_fwd_kernel");
-  return UIC_OK;
+    UIC_LAUNCH_CHECK("attn_fwd_fast_kernel");
+    return UIC_OK;
+  }
+  if (p.dtype == UIC_BF16) return launch_attn(attn_fwd_kernel<bf16_t>, p, NTHREADS, lds, s, "attn_fwd_kernel");
+  return launch_attn(attn_fwd_kernel<float>, p, NTHREADS, lds, s, "attn_fwd_kernel");
 }
 
-int uic_attention_bwd_step_launch(const UicAttnParams& p, hipStream_t s) {
-  UIC_TRY(check_common(p.dtype, p.N, p.R, p.A, p.H));
+int uic_attention_bwd_step_launch(const UicAttnParams& p, hipStream_t s, int* kernel_id) {
+  UIC_TRY(check_common("attention_bwd_step", p.dtype, p.N, p.R, p.A, p.H));
   UIC_REQUIRE(p.att_h && p.p_att && p.att && p.w_alpha && p.alpha && p.dctx && p.de && p.d_att_h,
               "attention_bwd_step: null pointer");
-  if (p.N == 0) return UIC_OK;
+  UIC_REQUIRE(p.lddctx >= p.H && p.dctx_nslab >= 0 && (!p.dctx_sum || p.ld_dctx_sum >= p.H),
+              "attention_bwd_step: lddctx=%d or ld_dctx_sum=%d < H=%d, or nslab=%d < 0", p.lddctx, p.ld_dctx_sum, p.H, p.dctx_nslab);
+  UIC_REQUIRE(!p.row_len || p.step >= 0, "attention_bwd_step: step=%d with a row_len", p.step);
+  UIC_REQUIRE(al16(p.p_att) && al16(p.att), "attention_bwd_step: p_att and att must be 16-byte aligned (every kernel reads them 16 bytes at a time)");
   const size_t lds = sizeof(float) * (2 * (size_t)p.A + p.H + 5 * ((p.R + 3) & ~3) + NWAVES * (size_t)p.A);
   UIC_REQUIRE(lds <= 160 * 1024, "attention_bwd_step: needs %zu B of LDS", lds);
-  if (fast_ok(p)) {
-    const int vec = p.dtype == UIC_BF16 ? 8 : 4;
-    const bool full = p.A == 64 * vec && p.H == 64 * vec;
-    if (p.dtype == UIC_BF16) {
-      if (full) hipLaunchKernelGGL((attn_bwd_step_fast_kernel<bf16_t, true>), dim3(p.N), dim3(NTHREADS), lds, s, p);
-      else hipLaunchKernelGGL((attn_bwd_step_fast_kernel<bf16_t, false>), dim3(p.N), dim3(NTHREADS), lds, s, p);
-    } else {
-      if (full) hipLaunchKernelGGL((attn_bwd_step_fast_kernel<float, true>), dim3(p.N), dim3(NTHREADS), lds, s, p);
-      else hipLaunchKernelGGL((attn_bwd_step_fast_kernel<float, false>), dim3(p.N), dim3(NTHREADS), lds, s, p);
-    }
-  } else if (p.dtype == UIC_BF16)
-    hipLaunchKernelGGL(attn_bwd_step_kernel<bf16_t>, dim3(p.N), dim3(NTHREADS), lds, s, p);
-  else
-    hipLaunchKernelGGL(attn_bwd_step_kernel<float>, dim3(p.N), dim3(NTHREADS), lds, s, p);
-  UIC_LAUNCH_CHECK("attn_bwd_step_kernel");
-  return UIC_OK;
+  const int vec = p.dtype == UIC_BF16 ? 8 : 4;
+  const bool fast = fast_ok(p, true), full = fast && p.A == 64 * vec && p.H == 64 * vec;
+  if (kernel_id) *kernel_id = full ? UIC_ATTN_FAST_FULL : fast ? UIC_ATTN_FAST : UIC_ATTN_GENERIC;
+  if (p.N == 0) return UIC_OK;
+  const char* what = "attn_bwd_step_kernel";
+  if (fast) {
+    if (p.dtype == UIC_BF16) return full ? launch_attn(attn_bwd_step_fast_kernel<bf16_t, true>, p, NTHREADS, lds, s, what)
+                                         : launch_attn(attn_bwd_step_fast_kernel<bf16_t, false>, p, NTHREADS, lds, s, what);
+    return full ? launch_attn(attn_bwd_step_fast_kernel<float, true>, p, NTHREADS, lds, s, what)
+                : launch_attn(attn_bwd_step_fast_kernel<float, false>, p, NTHREADS, lds, s, what);
+  }
+  if (p.dtype == UIC_BF16) return launch_attn(attn_bwd_step_kernel<bf16_t>, p, NTHREADS, lds, s, what);
+  return launch_attn(attn_bwd_step_kernel<float>, p, NTHREADS, lds, s, what);
 }
 
-int uic_attention_bwd_accum_launch(const UicAttnAccumParams& p, hipStream_t s) {
-  UIC_TRY(check_common(p.dtype, p.N, p.R, p.A, p.H));
+int uic_attention_bwd_accum_launch(const UicAttnAccumParams& p, hipStream_t s, int* kernel_id) {
+  UIC_TRY(check_common("attention_bwd_accum", p.dtype, p.N, p.R, p.A, p.H));
   UIC_REQUIRE(p.T > 0, "attention_bwd_accum: T=%d", p.T);
   UIC_REQUIRE(p.att_h_all && p.alpha_all && p.de_all && p.dctx_all && p.p_att && p.w_alpha && p.d_att && p.d_p_att &&
                   p.d_walpha_part, "attention_bwd_accum: null pointer");
-  if (p.N == 0) return UIC_OK;
+  UIC_REQUIRE(p.lddctx >= p.H, "attention_bwd_accum: lddctx=%d < H=%d", p.lddctx, p.H);
   const int Rp = (p.R + 3) & ~3;
   // measured at the benchmark shapes: PART 1 (f32 FMAs over LDS-staged rows) 42 -> 32 us with 8 waves per workgroup, PART 2
   // (one reciprocal per element) 110 us with 4 waves, 118 with 8
   // round 6 forms (above): PART 2 for bf16 with an even split of A into 4-column chunks, PART 1 wherever a lane's 16-byte loads
   // and stores are aligned
-  const bool p1_new = p.H % 4 == 0 && p.lddctx % 4 == 0 && p.dctx_step_stride % 4 == 0 && ((uintptr_t)p.dctx_all & 15) == 0 && ((uintptr_t)p.d_att & 15) == 0;
-  const bool p2_new = p.dtype == UIC_BF16 && p.A % 8 == 0 && ((uintptr_t)p.att_h_all & 15) == 0 && ((uintptr_t)p.w_alpha & 15) == 0 &&
+  const bool p1_new = p.H % 4 == 0 && p.lddctx % 4 == 0 && p.dctx_step_stride % 4 == 0 && al16(p.dctx_all);
+  const bool p2_new = p.dtype == UIC_BF16 && p.A % 8 == 0 && al16(p.att_h_all) && al16(p.w_alpha) &&
                       ((uintptr_t)p.p_att & 7) == 0 && ((uintptr_t)p.d_p_att & 7) == 0;
+  // what no kernel honours: both PART 1 kernels store d att' 16 bytes at a time, and the first PART 2 kernel reads p_att and writes
+  // d p_att 16 bytes at a time (the round-6 one 8).  att_h_all, w_alpha and d ctx are read one word at a time by the first forms.
+  UIC_REQUIRE(al16(p.d_att), "attention_bwd_accum: d_att must be 16-byte aligned");
+  UIC_REQUIRE(p2_new || (al16(p.p_att) && al16(p.d_p_att)), "attention_bwd_accum: p_att and d_p_att must be 16-byte aligned (8-byte for the bf16 kernel)");
   const size_t lds1n = sizeof(float) * (size_t)p.R * ((p.T + P1_TCH - 1) / P1_TCH * P1_TCH);
   const size_t lds2n = sizeof(float) * ((size_t)p.T * (p.A / 2 + Rp) + 4 * (size_t)(p.A / 2) + 4);
   UIC_REQUIRE(lds1n <= 160 * 1024 && lds2n <= 160 * 1024, "attention_bwd_accum: needs %zu B of LDS (T=%d)", lds1n > lds2n ? lds1n : lds2n, p.T);
+  const int nthreads1 = 512, nthreads2 = 256;
+  const size_t lds1 = sizeof(float) * ((size_t)p.T * (p.H + Rp));
+  const size_t lds2 = sizeof(float) * ((size_t)p.T * (p.A + Rp) + p.A + (nthreads2 / 64) * (size_t)p.A);
+  UIC_REQUIRE(lds1 <= 160 * 1024 && lds2 <= 160 * 1024, "attention_bwd_accum: needs %zu B of LDS (T=%d)", lds1 > lds2 ? lds1 : lds2, p.T);
+  if (kernel_id) *kernel_id = (p1_new ? UIC_ATTN_ACCUM_P1_R6 : 0) | (p2_new ? UIC_ATTN_ACCUM_P2_R6 : 0);
+  if (p.N == 0) return UIC_OK;
   if (p2_new) {
     if (lds2n > 64 * 1024) UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)attn_bwd_accum_p2_bf16_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2n), "hipFuncSetAttribute"));
     hipLaunchKernelGGL(attn_bwd_accum_p2_bf16_kernel, dim3(p.N, 2), dim3(256), lds2n, s, p);
@@ -932,14 +974,10 @@ int uic_attention_bwd_accum_launch(const UicAttnAccumParams& p, hipStream_t s) {
     if (lds1n > 64 * 1024) UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)attn_bwd_accum_p1_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1n), "hipFuncSetAttribute"));
     hipLaunchKernelGGL(attn_bwd_accum_p1_kernel, dim3(p.N), dim3(512), lds1n, s, p);
   }
-  const int nthreads1 = 512, nthreads2 = 256;
-  const size_t lds1 = sizeof(float) * ((size_t)p.T * (p.H + Rp));
-  const size_t lds2 = sizeof(float) * ((size_t)p.T * (p.A + Rp) + p.A + (nthreads2 / 64) * (size_t)p.A);
-  UIC_REQUIRE(lds1 <= 160 * 1024 && lds2 <= 160 * 1024, "attention_bwd_accum: needs %zu B of LDS (T=%d)", lds1 > lds2 ? lds1 : lds2, p.T);
 #define ACCUM_LAUNCH(TT)                                                                                                          \
   do {                                                                                                                            \
-    if (lds1 > 64 * 1024) UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)attn_bwd_accum_kernel<TT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1), "hipFuncSetAttribute")); \
-    if (lds2 > 64 * 1024) UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)attn_bwd_accum_kernel<TT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2), "hipFuncSetAttribute")); \
+    if (!p1_new && lds1 > 64 * 1024) UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)attn_bwd_accum_kernel<TT, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds1), "hipFuncSetAttribute")); \
+    if (!p2_new && lds2 > 64 * 1024) UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)attn_bwd_accum_kernel<TT, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2), "hipFuncSetAttribute")); \
     if (!p2_new) hipLaunchKernelGGL((attn_bwd_accum_kernel<TT, 2>), dim3(p.N), dim3(nthreads2), lds2, s, p);                        \
     if (!p1_new) hipLaunchKernelGGL((attn_bwd_accum_kernel<TT, 1>), dim3(p.N), dim3(nthreads1), lds1, s, p);                        \
   } while (0)

@@ -357,11 +357,12 @@ struct UicAttnParams {
   float* de;               // [N,R]
   void* d_att_h;           // [N,A] operand dtype
   // backward step, optional: rows whose caption has no live position at or behind this decode step (step >= row_len[n]) carry an
-  // all-zero gradient -- the fast kernel writes their zeros without reading their 74 KB of operands
+  // all-zero gradient -- every step kernel writes their zeros without reading their 74 KB of operands
   const int* row_len; int step;
 };
-int uic_attention_fwd_launch(const UicAttnParams& p, hipStream_t s);
-int uic_attention_bwd_step_launch(const UicAttnParams& p, hipStream_t s);
+// kernel_id (host, optional): UIC_ATTN_* of include/uic_hip.h, the kernel the call chose (set for N == 0 too, not for a refused call)
+int uic_attention_fwd_launch(const UicAttnParams& p, hipStream_t s, int* kernel_id = nullptr);
+int uic_attention_bwd_step_launch(const UicAttnParams& p, hipStream_t s, int* kernel_id = nullptr);
 
 struct UicAttnAccumParams {
   int dtype, N, R, A, H, T;          // T = number of executed decode steps
@@ -375,9 +376,9 @@ struct UicAttnAccumParams {
   void* d_p_att;           // [N,R,A] operand dtype out
   float* d_walpha_part;    // [N,A+1] per-row partial of (d w_alpha, d b_alpha)
   const int* row_len;      // optional [N]: decode steps >= row_len[n] of row n carry zero gradients (d e = d ctx = 0: the caption
-                           // ended): the round-6 kernels sum over the row's first min(T, row_len[n]) steps only -- the same sums
+                           // ended): every kernel sums over the row's first min(T, row_len[n]) steps only -- the same sums
 };
-int uic_attention_bwd_accum_launch(const UicAttnAccumParams& p, hipStream_t s);
+int uic_attention_bwd_accum_launch(const UicAttnAccumParams& p, hipStream_t s, int* kernel_id = nullptr);   // UIC_ATTN_ACCUM_* bits
 
 // ---------------------------------------------------------------- persistent recurrence (rnn_persist.hip)
 // Decode steps [t0, t1) of the TopDown recurrence (P/models/AttModel.py:129-154, :430-446, :538-558) in ONE launch.
