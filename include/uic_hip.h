@@ -1196,6 +1196,120 @@ int uic_transformer_sample_beam(const uic_transformer_dims* d, const uic_transfo
 int uic_transformer_beam_done_lists(const uic_transformer_dims* d, void* workspace, int32_t L, int32_t beam_size, int32_t* done_count,
                                     float* done_p, int64_t* done_seq, float* done_lp, void* stream);
 
+/* ---------------------------------------------------------------- the AdaAtt captioners, eval mode (csrc/adaatt.hip)
+ * The `adaatt` / `adaattmo` caption models ("Knowing when to look": AdaAtt_lstm, AdaAtt_attention, AdaAttCore, AdaAttModel,
+ * AdaAttMOModel of P/models/AttModel.py:256-418, 657-667): the teacher-forced forward pass and decoding.  Training is not built.
+ *
+ * The pointwise part of AdaAtt_lstm.forward for one layer (:304-329).  sums f32 [N, ld_sums] holds the all_input_sums: chunks in,
+ * forget, out (sigmoid), then the transform -- tanh of one chunk (maxout = 0) or the max of two chunks (maxout = 1), so
+ * ld_sums >= (4 + maxout) H.  next_c = forget c_prev + in transform (c_prev f32 [N, H] or NULL = 0), next_h = out tanh(next_c).
+ * n5 f32 [N, ld_n5] (optional; may be the next H columns of the sums buffer) gives the sentinel of the last layer,
+ * fake = sigmoid(n5) tanh(next_c) (:328-329); n5 and fake_out come together or not at all.
+ * c_out f32 [N, H]; h_out [N, ld_h] and fake_out [N, ld_fake] in `dtype`.  bf16 takes the hardware exponential forms of
+ * sigmoid / tanh, f32 the libm ones.
+ * REFUSED (non-zero return, uic_last_error_string names the cause, NOTHING is launched and no output is touched): a dtype other
+ * than the two, N < 0, H no positive multiple of 4, maxout outside {0, 1}, a null required pointer, n5 without fake_out or the
+ * reverse, a leading dimension below its width or no multiple of 4, an operand not aligned to four of its elements.
+ * N == 0 is a successful no-op. */
+int uic_adaatt_cell_fwd(int32_t dtype, int32_t N, int32_t H, int32_t maxout, const float* sums, int32_t ld_sums, const float* n5,
+                        int32_t ld_n5, const float* c_prev, float* c_out, void* h_out, int32_t ld_h, void* fake_out, int32_t ld_fake,
+                        void* stream);
+/* AdaAtt_attention.forward between its linears (:383-402), conventions of uic_attention_fwd_strided: the queries fr_e, hl_e
+ * [N, ld_q >= A] are f32; p_att [N / row_div, R, A], att [N / row_div, R, H], fr, hl [N, ld_x >= H] and out [N, ld_out >= H] are
+ * in `dtype`; w_alpha [A], b_alpha [1], mask [N / row_div, ld_mask >= R] (optional) and PI [N, R + 1] are f32.  A and H multiples
+ * of 4 (f32) / 8 (bf16) = vec.  Row n reads the features of image n / row_div (the beams of an image share them).
+ *   e_0 = w . tanh(fr_e[n] + hl_e[n]) + b,   e_r = w . tanh(p_att[n / row_div, r - 1] + hl_e[n]) + b  (r = 1 .. R)
+ *   PI = softmax over the R + 1 slots (maximum subtracted); with a mask m: PI_0 *= m_0, PI_r *= m_{r-1}, PI /= sum PI
+ *        (the reference's cat([m[:, :1], m]), :396-397)
+ *   out[n] = PI_0 fr[n] + sum_r PI_r att[n / row_div, r - 1] + hl[n]
+ * where the sequencer has made fr = relu(fr_linear(fake)), fr_e = fr_embed(fr), hl = tanh(ho_linear(h)), hl_e = ho_embed(hl).
+ * One workgroup owns a row; no atomics: a run is bit-reproducible.
+ * REFUSED as above: a bad dtype, N < 0, R, A or H < 1, A or H no multiple of vec, row_div < 1 or not dividing N, a null pointer
+ * other than mask, a leading dimension below its width, ld_x / ld_out no multiple of vec, p_att, att, fr, hl or out not 16-byte
+ * aligned, more than 160 KB of LDS (4 (3A + R + 1 rounded up to 4 + 4H) B; the launcher asks for what exceeds 64 KB).
+ * N == 0 is a successful no-op.  tests/test_gpu_adaatt_ops.py holds both operators against float64, element by element. */
+int uic_adaatt_attention_fwd(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, int32_t row_div, const float* fr_e,
+                             const float* hl_e, int32_t ld_q, const void* fr, const void* hl, int32_t ld_x, const void* p_att,
+                             const void* att, const float* w_alpha, const float* b_alpha, const float* mask, int32_t ld_mask, float* PI,
+                             void* out, int32_t ld_out, void* stream);
+
+#define UIC_ADAATT_MAX_LAYERS 2
+typedef struct uic_adaatt_dims {
+  int32_t N;             /* images (decode rows are N * beam) */
+  int32_t R;             /* regions per image after clip_att */
+  int32_t D;             /* opt.att_feat_size (a multiple of 8: the caller zero-pads) */
+  int32_t Dfc;           /* opt.fc_feat_size */
+  int32_t H;             /* opt.rnn_size == opt.input_encoding_size == opt.att_hid_size (:385-386 need them equal) */
+  int32_t V1;            /* vocab_size + 1 */
+  int32_t S;             /* columns of the labels the workspace is sized for: seq_length + 2 */
+  int32_t layers;        /* opt.num_layers, 1 .. UIC_ADAATT_MAX_LAYERS */
+  int32_t maxout;        /* 0: adaatt, 1: adaattmo */
+  int32_t logit_layers;  /* as uic_topdown_dims */
+  int32_t use_bn;        /* 0, 1, 2: the BatchNorm1d layers of att_embed, running statistics */
+  int32_t dtype;
+  int32_t beam;          /* decode rows per image the workspace holds (1 unless beam search) */
+} uic_adaatt_dims;
+
+/* f32 masters in AdaAttModel.state_dict() order.  G = 4 + maxout. */
+typedef struct uic_adaatt_weights {
+  const float* embed_w;                                             /* embed.0.weight [V1, H] */
+  const float* fc_w; const float* fc_b;                             /* fc_embed.0 [H, Dfc] */
+  const float* att_bn0_w; const float* att_bn0_b; const float* att_bn0_rm; const float* att_bn0_rv;   /* att_embed.0, use_bn >= 1 */
+  const float* att_w; const float* att_b;                           /* att_embed's Linear [H, D] */
+  const float* att_bn4_w; const float* att_bn4_b; const float* att_bn4_rm; const float* att_bn4_rv;   /* att_embed.4, use_bn == 2 */
+  const float* logit_h_w[UIC_MAX_LOGIT_LAYERS - 1]; const float* logit_h_b[UIC_MAX_LOGIT_LAYERS - 1];   /* logit.{3l} [H, H] */
+  const float* logit_w; const float* logit_b;                       /* the vocabulary layer [V1, H] */
+  const float* ctx2att_w; const float* ctx2att_b;                   /* [H, H] */
+  const float* w2h_w; const float* w2h_b;                           /* core.lstm.w2h [G H, H] */
+  const float* v2h_w; const float* v2h_b;                           /* core.lstm.v2h [G H, H] */
+  const float* i2h_w[UIC_ADAATT_MAX_LAYERS - 1]; const float* i2h_b[UIC_ADAATT_MAX_LAYERS - 1];   /* core.lstm.i2h.l [G H, H] */
+  const float* h2h_w[UIC_ADAATT_MAX_LAYERS]; const float* h2h_b[UIC_ADAATT_MAX_LAYERS];           /* core.lstm.h2h.l [G H, H] */
+  const float* r_w2h_w; const float* r_w2h_b; const float* r_v2h_w; const float* r_v2h_b;         /* layers == 1 */
+  const float* r_i2h_w; const float* r_i2h_b;                       /* layers > 1 */
+  const float* r_h2h_w; const float* r_h2h_b;                       /* [H, H] */
+  const float* fr_linear_w; const float* fr_linear_b;               /* core.attention.fr_linear.0 */
+  const float* fr_embed_w; const float* fr_embed_b;
+  const float* ho_linear_w; const float* ho_linear_b;               /* core.attention.ho_linear.0 */
+  const float* ho_embed_w; const float* ho_embed_b;
+  const float* alpha_w; const float* alpha_b;                       /* core.attention.alpha_net [1, H], [1] */
+  const float* att2h_w; const float* att2h_b;
+} uic_adaatt_weights;
+
+/* One workspace serves every call below; it also holds the operand-dtype weight copies, the stacked gate matrices
+ * [w2h ; r_w2h], [h2h ; r_h2h], [v2h ; r_v2h] (the sentinel costs no extra launch) and their summed biases, which every call
+ * rebuilds from the masters.  0: the dims are refused (uic_last_error_string). */
+size_t uic_adaatt_workspace_bytes(const uic_adaatt_dims* d);
+/* AttModel._prepare_feature (:107-117) in eval mode: fc_feats [N, Dfc], att_feats [N, R, D], att_masks [N, R] or NULL, f32.
+ * fc_out [N, H], att_out / p_att_out [N, R, H] f32 (rounded through the operand dtype). */
+int uic_adaatt_prepare_feature(const uic_adaatt_dims* d, const uic_adaatt_weights* w, const float* fc_feats, const float* att_feats,
+                               const float* att_masks, void* workspace, float* fc_out, float* att_out, float* p_att_out, void* stream);
+/* AttModel._forward (:119-156) in eval mode over the first Tq columns of seq [N, ld_seq] int64 (Tq = seq.size(1) - 1 <= S - 1):
+ * steps 0 .. s_run - 1 run (s_run < Tq: the early break of :148-151, found by the caller); logprobs_out [N, Tq, V1] f32 gets
+ * their rows, the rows behind the break are left as the caller made them (zeros in the reference). */
+int uic_adaatt_forward(const uic_adaatt_dims* d, const uic_adaatt_weights* w, const float* fc_feats, const float* att_feats,
+                       const float* att_masks, const int64_t* seq, int32_t ld_seq, int32_t Tq, int32_t s_run, void* workspace,
+                       float* logprobs_out, void* stream);
+/* AttModel.get_logprobs_state (:158-165) from prepared features (f32, as uic_adaatt_prepare_feature returns them, one image per
+ * row): it [N] int64, state h_in / c_in [layers, N, H] f32 -> logprobs [N, V1], h_out / c_out [layers, N, H]. */
+int uic_adaatt_logprobs_state(const uic_adaatt_dims* d, const uic_adaatt_weights* w, const int64_t* it, const float* fc, const float* att,
+                              const float* p_att, const float* att_masks, const float* h_in, const float* c_in, void* workspace,
+                              float* logprobs, float* h_out, float* c_out, void* stream);
+/* AttModel._sample (:198-253, beam_size = 1): <bos> = 0, arg-max (sample_max) or a multinomial draw from
+ * softmax(logprobs / temperature), decoding_constraint as :220-223.  All L steps are enqueued with no host read-back; once every
+ * row has finished the remaining entries stay 0, as after the reference's break.  seq [N, L] int64, seq_logp [N, L] f32. */
+int uic_adaatt_sample(const uic_adaatt_dims* d, const uic_adaatt_weights* w, const float* fc_feats, const float* att_feats,
+                      const float* att_masks, int32_t L, int32_t sample_max, float temperature, int32_t decoding_constraint,
+                      uint32_t seed, void* workspace, int64_t* seq, float* seq_logp, void* stream);
+/* AttModel._sample_beam over CaptionModel.beam_search (:167-196, P/models/CaptionModel.py:33-177) with group_size = 1, all images
+ * at once: rows = (image, beam), beam_size == d->beam <= UIC_BEAM_MAX.  The beams of an image share its features (row_div of the
+ * attention); the states follow the surviving parents.  Outputs as uic_topdown_sample_beam. */
+int uic_adaatt_sample_beam(const uic_adaatt_dims* d, const uic_adaatt_weights* w, const float* fc_feats, const float* att_feats,
+                           const float* att_masks, int32_t L, int32_t beam_size, int32_t decoding_constraint, int32_t max_ppl,
+                           void* workspace, int64_t* seq, float* seq_logp, void* stream);
+/* The done list of the call above, read from the workspace right after it; layout as uic_topdown_beam_done_lists. */
+int uic_adaatt_beam_done_lists(const uic_adaatt_dims* d, void* workspace, int32_t L, int32_t beam_size, int32_t* done_count,
+                               float* done_p, int64_t* done_seq, float* done_lp, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -208,6 +208,86 @@ def mha_lds_bytes(Sk, d_k):
     return (Sk * (d_k + 1) + Sk * d_k + 4 * (Sk + d_k)) * 4
 
 
+BEAM_MAX = 16              # UIC_BEAM_MAX
+ADAATT_MAX_LAYERS = 2      # UIC_ADAATT_MAX_LAYERS
+LDS_BYTES = 160 * 1024     # per workgroup on gfx950
+
+
+class AdaAttDims(C.Structure):
+    """uic_adaatt_dims"""
+    _fields_ = [(n, C.c_int32) for n in ("N", "R", "D", "Dfc", "H", "V1", "S", "layers", "maxout", "logit_layers", "use_bn", "dtype", "beam")]
+
+
+class AdaAttWeights(C.Structure):
+    """uic_adaatt_weights"""
+    _fields_ = [(f, C.c_void_p) for f in ("embed_w", "fc_w", "fc_b", "att_bn0_w", "att_bn0_b", "att_bn0_rm", "att_bn0_rv", "att_w", "att_b",
+                                          "att_bn4_w", "att_bn4_b", "att_bn4_rm", "att_bn4_rv")] + \
+               [("logit_h_w", C.c_void_p * (MAX_LOGIT_LAYERS - 1)), ("logit_h_b", C.c_void_p * (MAX_LOGIT_LAYERS - 1))] + \
+               [(f, C.c_void_p) for f in ("logit_w", "logit_b", "ctx2att_w", "ctx2att_b", "w2h_w", "w2h_b", "v2h_w", "v2h_b")] + \
+               [("i2h_w", C.c_void_p * (ADAATT_MAX_LAYERS - 1)), ("i2h_b", C.c_void_p * (ADAATT_MAX_LAYERS - 1)),
+                ("h2h_w", C.c_void_p * ADAATT_MAX_LAYERS), ("h2h_b", C.c_void_p * ADAATT_MAX_LAYERS)] + \
+               [(f, C.c_void_p) for f in ("r_w2h_w", "r_w2h_b", "r_v2h_w", "r_v2h_b", "r_i2h_w", "r_i2h_b", "r_h2h_w", "r_h2h_b",
+                                          "fr_linear_w", "fr_linear_b", "fr_embed_w", "fr_embed_b", "ho_linear_w", "ho_linear_b",
+                                          "ho_embed_w", "ho_embed_b", "alpha_w", "alpha_b", "att2h_w", "att2h_b")]
+
+
+def adaatt_weight_keys(layers, use_bn=0, logit_layers=1):
+    """[(struct field, index or None, reference state_dict key)] of uic_adaatt_weights in AdaAttModel.state_dict() order
+    (P/models/AttModel.py:73-92, 271-283, 354-368); `num_batches_tracked` of the BatchNorm layers has no field."""
+    lin = 1 if use_bn else 0
+    out = [("embed_w", None, "embed.0.weight"), ("fc_w", None, "fc_embed.0.weight"), ("fc_b", None, "fc_embed.0.bias")]
+    if use_bn:
+        out += [("att_bn0_w", None, "att_embed.0.weight"), ("att_bn0_b", None, "att_embed.0.bias"),
+                ("att_bn0_rm", None, "att_embed.0.running_mean"), ("att_bn0_rv", None, "att_embed.0.running_var")]
+    out += [("att_w", None, "att_embed.%d.weight" % lin), ("att_b", None, "att_embed.%d.bias" % lin)]
+    if use_bn == 2:
+        out += [("att_bn4_w", None, "att_embed.4.weight"), ("att_bn4_b", None, "att_embed.4.bias"),
+                ("att_bn4_rm", None, "att_embed.4.running_mean"), ("att_bn4_rv", None, "att_embed.4.running_var")]
+    if logit_layers > 1:
+        for l in range(logit_layers - 1):
+            out += [("logit_h_w", l, "logit.%d.weight" % (3 * l)), ("logit_h_b", l, "logit.%d.bias" % (3 * l))]
+        out += [("logit_w", None, "logit.%d.weight" % (3 * (logit_layers - 1))), ("logit_b", None, "logit.%d.bias" % (3 * (logit_layers - 1)))]
+    else:
+        out += [("logit_w", None, "logit.weight"), ("logit_b", None, "logit.bias")]
+    out += [("ctx2att_w", None, "ctx2att.weight"), ("ctx2att_b", None, "ctx2att.bias")]
+    p = "core.lstm."
+    out += [("w2h_w", None, p + "w2h.weight"), ("w2h_b", None, p + "w2h.bias"), ("v2h_w", None, p + "v2h.weight"), ("v2h_b", None, p + "v2h.bias")]
+    for l in range(layers - 1):
+        out += [("i2h_w", l, p + "i2h.%d.weight" % l), ("i2h_b", l, p + "i2h.%d.bias" % l)]
+    for l in range(layers):
+        out += [("h2h_w", l, p + "h2h.%d.weight" % l), ("h2h_b", l, p + "h2h.%d.bias" % l)]
+    if layers == 1:
+        out += [("r_w2h_w", None, p + "r_w2h.weight"), ("r_w2h_b", None, p + "r_w2h.bias"),
+                ("r_v2h_w", None, p + "r_v2h.weight"), ("r_v2h_b", None, p + "r_v2h.bias")]
+    else:
+        out += [("r_i2h_w", None, p + "r_i2h.weight"), ("r_i2h_b", None, p + "r_i2h.bias")]
+    out += [("r_h2h_w", None, p + "r_h2h.weight"), ("r_h2h_b", None, p + "r_h2h.bias")]
+    a = "core.attention."
+    for f, k in (("fr_linear", "fr_linear.0"), ("fr_embed", "fr_embed"), ("ho_linear", "ho_linear.0"), ("ho_embed", "ho_embed"),
+                 ("alpha", "alpha_net"), ("att2h", "att2h")):
+        out += [(f + "_w", None, a + k + ".weight"), (f + "_b", None, a + k + ".bias")]
+    return out
+
+
+def adaatt_weights(tensors, layers, use_bn=0, logit_layers=1):
+    """Fill a uic_adaatt_weights from {reference key: contiguous f32 device tensor}."""
+    w = AdaAttWeights()
+    for f, i, k in adaatt_weight_keys(layers, use_bn, logit_layers):
+        t = tensors[k]
+        assert t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda, k
+        if i is None:
+            setattr(w, f, t.data_ptr())
+        else:
+            getattr(w, f)[i] = t.data_ptr()
+    return w
+
+
+def adaatt_attention_lds_bytes(R, A, H):
+    """LDS of one uic_adaatt_attention_fwd workgroup: hl_e, fr_e and w_alpha [A], the R + 1 slots (rounded up to 4), per wave (4) a
+    partial output row [H], f32."""
+    return 4 * (3 * A + (R + 1 + 3) // 4 * 4 + 4 * H)
+
+
 GCN_MAX_LAYERS = 3
 
 
@@ -487,6 +567,18 @@ _SIGS = {
     "uic_transformer_sample_beam": (C.c_int, [C.POINTER(TransformerDims), C.POINTER(TransformerWeights)] + [C.c_void_p] * 3 +
                                     [C.c_int32] * 4 + [C.c_void_p] * 4),
     "uic_transformer_beam_done_lists": (C.c_int, [C.POINTER(TransformerDims), C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
+    "uic_adaatt_cell_fwd": (C.c_int, [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                      C.c_void_p, C.c_int32, C.c_void_p]),
+    "uic_adaatt_attention_fwd": (C.c_int, [C.c_int32] * 6 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32] +
+                                 [C.c_void_p] * 5 + [C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "uic_adaatt_workspace_bytes": (C.c_size_t, [C.POINTER(AdaAttDims)]),
+    "uic_adaatt_prepare_feature": (C.c_int, [C.POINTER(AdaAttDims), C.POINTER(AdaAttWeights)] + [C.c_void_p] * 8),
+    "uic_adaatt_forward": (C.c_int, [C.POINTER(AdaAttDims), C.POINTER(AdaAttWeights)] + [C.c_void_p] * 4 + [C.c_int32] * 3 + [C.c_void_p] * 3),
+    "uic_adaatt_logprobs_state": (C.c_int, [C.POINTER(AdaAttDims), C.POINTER(AdaAttWeights)] + [C.c_void_p] * 12),
+    "uic_adaatt_sample": (C.c_int, [C.POINTER(AdaAttDims), C.POINTER(AdaAttWeights)] + [C.c_void_p] * 3 +
+                          [C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_uint32] + [C.c_void_p] * 4),
+    "uic_adaatt_sample_beam": (C.c_int, [C.POINTER(AdaAttDims), C.POINTER(AdaAttWeights)] + [C.c_void_p] * 3 + [C.c_int32] * 4 + [C.c_void_p] * 4),
+    "uic_adaatt_beam_done_lists": (C.c_int, [C.POINTER(AdaAttDims), C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 5),
 }
 EXPORTS = tuple(_SIGS)
 

@@ -9,7 +9,7 @@ reference (eval_ensemble.py calls model.eval() before anything else).  There is 
 import torch
 import torch.nn as nn
 
-from .AttModel import AttModel
+from .AttModel import AttModel, TopDownModel
 from .CaptionModel import CaptionModel
 from .. import topdown_engine as TE
 
@@ -21,8 +21,9 @@ class AttEnsemble(AttModel):
         if not 1 <= len(models) <= TE._lib.ENSEMBLE_MAX:
             raise ValueError("an ensemble has 1..%d members, got %d" % (TE._lib.ENSEMBLE_MAX, len(models)))
         for i, m in enumerate(models):
-            if not isinstance(m, AttModel) or isinstance(m, AttEnsemble):
-                raise TypeError("ensemble member %d is a %s, not an AttModel" % (i, type(m).__name__))
+            # (AdaAttModel is an AttModel too, but has no TopDownEngine for the ensemble sequencers to step)
+            if not isinstance(m, TopDownModel):
+                raise TypeError("ensemble member %d is a %s, not a TopDownModel" % (i, type(m).__name__))
             if m.vocab_size != models[0].vocab_size or m.seq_length != models[0].seq_length:
                 raise ValueError("ensemble member %d has vocab_size=%d seq_length=%d, member 0 vocab_size=%d seq_length=%d: the members "
                                  "must share the vocabulary and the caption length" %

@@ -6,12 +6,20 @@ The nn.Module tree below exists only to own parameters under the reference's nam
 round-trip the reference's `model_i2t-best.pth` unchanged; none of these sub-modules'
 `forward` is ever called.  There is no eager fallback: without the HIP library, or on a
 CPU tensor, every call raises.
+
+AdaAttModel / AdaAttMOModel (P/models/AttModel.py:256-418, 657-667) follow at the end of the file under the same
+contract, for evaluation and decoding only: they are computed by the uic_adaatt_* sequencers (csrc/adaatt.hip),
+not by a TopDownEngine.
 """
+import ctypes as C
+
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .CaptionModel import CaptionModel
 from .. import _lib
+from .._lib import check, ptr, stream
 from ..topdown_engine import TopDownEngine
 
 
@@ -379,3 +387,251 @@ class TopDownModel(AttModel):
         super(TopDownModel, self).__init__(opt)
         self.num_layers = 2
         self.core = TopDownCore(opt)
+
+
+# ---------------------------------------------------------------------------------------------------------------- AdaAtt
+class AdaAtt_lstm(nn.Module):
+    """P/models/AttModel.py:256-283: parameters only."""
+
+    def __init__(self, opt, use_maxout=True):
+        super(AdaAtt_lstm, self).__init__()
+        self.use_maxout = use_maxout
+        self.num_layers = opt.num_layers
+        G = (4 + (use_maxout == True)) * opt.rnn_size       # noqa: E712 (the reference's expression)
+        self.w2h = nn.Linear(opt.input_encoding_size, G)
+        self.v2h = nn.Linear(opt.rnn_size, G)
+        self.i2h = nn.ModuleList([nn.Linear(opt.rnn_size, G) for _ in range(self.num_layers - 1)])
+        self.h2h = nn.ModuleList([nn.Linear(opt.rnn_size, G) for _ in range(self.num_layers)])
+        if self.num_layers == 1:
+            self.r_w2h = nn.Linear(opt.input_encoding_size, opt.rnn_size)
+            self.r_v2h = nn.Linear(opt.rnn_size, opt.rnn_size)
+        else:
+            self.r_i2h = nn.Linear(opt.rnn_size, opt.rnn_size)
+        self.r_h2h = nn.Linear(opt.rnn_size, opt.rnn_size)
+
+
+class AdaAtt_attention(nn.Module):
+    """P/models/AttModel.py:344-368: parameters only."""
+
+    def __init__(self, opt):
+        super(AdaAtt_attention, self).__init__()
+        self.fr_linear = nn.Sequential(nn.Linear(opt.rnn_size, opt.input_encoding_size), nn.ReLU(), nn.Dropout(opt.drop_prob_lm))
+        self.fr_embed = nn.Linear(opt.input_encoding_size, opt.att_hid_size)
+        self.ho_linear = nn.Sequential(nn.Linear(opt.rnn_size, opt.input_encoding_size), nn.Tanh(), nn.Dropout(opt.drop_prob_lm))
+        self.ho_embed = nn.Linear(opt.input_encoding_size, opt.att_hid_size)
+        self.alpha_net = nn.Linear(opt.att_hid_size, 1)
+        self.att2h = nn.Linear(opt.rnn_size, opt.rnn_size)
+
+
+class AdaAttCore(nn.Module):
+    def __init__(self, opt, use_maxout=False):
+        super(AdaAttCore, self).__init__()
+        self.lstm = AdaAtt_lstm(opt, use_maxout)
+        self.attention = AdaAtt_attention(opt)
+
+
+class AdaAttModel(AttModel):
+    """The adaptive-attention captioner (P/models/AttModel.py:657-660) computed by csrc/adaatt.hip -- evaluation and decoding only;
+    training is not built.  There is no eager fallback: without the HIP library, or on a CPU tensor, every call raises."""
+    eval_only = True            # Trainer refuses to build a training run around it
+    supports_grad_sink = False
+    use_maxout = False
+    _TRAINING = "%s: evaluation and decoding only; training is not built (call model.eval())"
+
+    def __init__(self, opt):
+        name = type(self).__name__
+        E, H, A = opt.input_encoding_size, opt.rnn_size, opt.att_hid_size
+        if not E == H == A:
+            # AdaAtt_attention.forward views fr_embed's output with input_encoding_size and cats it with p_att_feats (:385-386), and
+            # adds h_out_linear [input_encoding_size] to the attended features [rnn_size] (:402): the reference fails at its first forward
+            raise NotImplementedError("%s: input_encoding_size=%r, rnn_size=%r and att_hid_size=%r must all be equal (the reference's "
+                                      "AdaAtt_attention fails at its first forward otherwise)" % (name, E, H, A))
+        if H % 8:
+            raise NotImplementedError("%s: rnn_size=%r must be a multiple of 8 (the GEMM operands are read in 16-byte pieces)" % (name, H))
+        if not 1 <= opt.num_layers <= _lib.ADAATT_MAX_LAYERS:
+            raise NotImplementedError("%s: num_layers=%r: the MI355X path supports 1..%d" % (name, opt.num_layers, _lib.ADAATT_MAX_LAYERS))
+        super(AdaAttModel, self).__init__(opt)
+        self.core = AdaAttCore(opt, self.use_maxout)
+        self._ws = None
+        self._padded = self._padded_key = None
+        self._done_beams = self._done_raw = None
+
+    # ------------------------------------------------------------------ engine plumbing
+    @property
+    def engine(self):
+        # (AttributeError: `getattr(model, 'engine', None)` is how Trainer and eval_utils ask whether a model has one)
+        raise AttributeError("%s has no TopDownEngine: it is computed by the uic_adaatt_* sequencers (csrc/adaatt.hip)" % type(self).__name__)
+
+    @property
+    def param_names(self):
+        return [k for k, _ in self.named_parameters()]
+
+    @property
+    def _D8(self):
+        """att_feat_size rounded up to a multiple of 8 (2053 with the reference's default use_box = 1): the features and att_embed's
+        input side are zero-padded up to it, as in TransformerModel."""
+        return (self.att_feat_size + 7) // 8 * 8
+
+    @property
+    def _Dfc8(self):
+        return (self.fc_feat_size + 7) // 8 * 8
+
+    def _dims(self, N, R, beam=1):
+        return _lib.AdaAttDims(N=N, R=R, D=self._D8, Dfc=self._Dfc8, H=self.rnn_size, V1=self.vocab_size + 1, S=self.seq_length + 2,
+                               layers=self.num_layers, maxout=int(self.use_maxout), logit_layers=self.logit_layers, use_bn=self.use_bn,
+                               dtype=_lib.dtype_id(self.compute_dtype), beam=beam)
+
+    def _tensors(self):
+        sd = dict(self.named_parameters())
+        sd.update(dict(self.named_buffers()))
+        t = {k: sd[k].detach() for _, _, k in _lib.adaatt_weight_keys(self.num_layers, self.use_bn, self.logit_layers)}
+        fills = {}
+        if self._D8 != self.att_feat_size:
+            # zero columns on the Linear; on BatchNorm1d(D) the identity (gamma 1, beta 0, mean 0, var 1) over zero features: nothing added
+            fills["att_embed.%d.weight" % (1 if self.use_bn else 0)] = (self._D8 - self.att_feat_size, 0.0)
+            if self.use_bn:
+                for k, v in (("weight", 1.0), ("bias", 0.0), ("running_mean", 0.0), ("running_var", 1.0)):
+                    fills["att_embed.0." + k] = (self._D8 - self.att_feat_size, v)
+        if self._Dfc8 != self.fc_feat_size:
+            fills["fc_embed.0.weight"] = (self._Dfc8 - self.fc_feat_size, 0.0)
+        if fills:
+            key = tuple((t[k].data_ptr(), t[k]._version) for k in fills)
+            if self._padded_key != key:
+                self._padded = {k: F.pad(t[k], (0, extra), value=v).contiguous() for k, (extra, v) in fills.items()}
+                self._padded_key = key
+            t.update(self._padded)
+        return t
+
+    def _prepare(self, fc_feats, att_feats, att_masks, beam=1):
+        """(lib, dims, weights, workspace, fc, att, masks) for one call: the region axis clipped (clip_att), the features zero-padded
+        to multiples of 8 columns, a workspace of the call's size."""
+        if self.training:
+            raise NotImplementedError(self._TRAINING % type(self).__name__)
+        lib = _lib.load()
+        att_feats, att_masks = self.clip_att(att_feats, att_masks)
+        if att_feats.shape[-1] != self.att_feat_size or fc_feats.shape[-1] != self.fc_feat_size:
+            raise ValueError("features have %d / %d columns, opt.fc_feat_size / att_feat_size are %d / %d"
+                             % (fc_feats.shape[-1], att_feats.shape[-1], self.fc_feat_size, self.att_feat_size))
+        fc = F.pad(fc_feats.float(), (0, self._Dfc8 - self.fc_feat_size)).contiguous()
+        att = F.pad(att_feats.float(), (0, self._D8 - self.att_feat_size)).contiguous()
+        am = att_masks.contiguous().float() if att_masks is not None else None
+        if not att.is_cuda or not fc.is_cuda:
+            raise RuntimeError("%s needs device tensors; got a %s tensor (there is no CPU fallback)" % (type(self).__name__, att.device))
+        d = self._dims(att.shape[0], att.shape[1], beam)
+        if _lib.adaatt_attention_lds_bytes(d.R, d.H, d.H) > _lib.LDS_BYTES:
+            raise NotImplementedError("%d regions at rnn_size %d: uic_adaatt_attention_fwd keeps a row's scores and partial sums in LDS (160 KB)"
+                                      % (d.R, d.H))
+        w = _lib.adaatt_weights(self._tensors(), self.num_layers, self.use_bn, self.logit_layers)
+        return lib, d, w, self._workspace(lib, d, att.device), fc, att, am
+
+    def _workspace(self, lib, d, device):
+        nbytes = lib.uic_adaatt_workspace_bytes(C.byref(d))
+        if nbytes == 0:
+            check(-1, "adaatt_workspace_bytes")
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != device:
+            self._ws = torch.empty(nbytes, dtype=torch.uint8, device=device)
+        return self._ws
+
+    # ------------------------------------------------------------------ reference call surface
+    def _forward(self, fc_feats, attri_feats, att_feats, seq, att_masks=None):
+        """P/models/AttModel.py:119-156 in eval mode: log-probs [N, seq.size(1) - 1, V + 1]; the steps behind the early break are zeros."""
+        with torch.no_grad():
+            if seq.shape[0] != fc_feats.shape[0]:
+                # features once per image, seq_per_img caption rows per image (the loader's validation batches): one row per caption
+                S = seq.shape[0] // fc_feats.shape[0]
+                fc_feats, att_feats = fc_feats.repeat_interleave(S, 0), att_feats.repeat_interleave(S, 0)
+                att_masks = att_masks.repeat_interleave(S, 0) if att_masks is not None else None
+            lib, d, w, ws, fc, att, am = self._prepare(fc_feats, att_feats, att_masks)
+            seq = seq.contiguous().long()
+            Tq = seq.shape[1] - 1
+            if not 1 <= Tq <= d.S - 1:
+                raise ValueError("seq has %d columns; the model scores 2..%d (seq_length + 2)" % (seq.shape[1], d.S))
+            logp = torch.zeros(d.N, Tq, d.V1, dtype=torch.float32, device=att.device)
+            check(lib.uic_adaatt_forward(C.byref(d), C.byref(w), ptr(fc), ptr(att), ptr(am), ptr(seq), seq.shape[1], Tq, self._steps_to_run(seq),
+                                         ptr(ws), ptr(logp), stream()), "adaatt_forward")
+        return logp
+
+    def _prepare_feature(self, fc_feats, att_feats, att_masks):
+        """P/models/AttModel.py:107-117 -> (fc', att', p_att, att_masks), f32 device tensors."""
+        with torch.no_grad():
+            lib, d, w, ws, fc, att, am = self._prepare(fc_feats, att_feats, att_masks)
+            H = self.rnn_size
+            fc_p = torch.empty(d.N, H, dtype=torch.float32, device=att.device)
+            att_p = torch.empty(d.N, d.R, H, dtype=torch.float32, device=att.device)
+            p_att = torch.empty(d.N, d.R, H, dtype=torch.float32, device=att.device)
+            check(lib.uic_adaatt_prepare_feature(C.byref(d), C.byref(w), ptr(fc), ptr(att), ptr(am), ptr(ws), ptr(fc_p), ptr(att_p), ptr(p_att),
+                                                 stream()), "adaatt_prepare_feature")
+        return fc_p, att_p, p_att, am
+
+    def get_logprobs_state(self, it, fc_feats, att_feats, p_att_feats, att_masks, state, t=0):
+        """P/models/AttModel.py:158-165: one decode step from prepared features -> (log-probs [N, V+1], new state);
+        state = (h, c), each [num_layers, N, H].  (`t` only numbers the dropout draws of a TopDown training step; unused here.)"""
+        if self.training:
+            raise NotImplementedError(self._TRAINING % type(self).__name__)
+        with torch.no_grad():
+            lib = _lib.load()
+            fc, att, p_att = fc_feats.contiguous().float(), att_feats.contiguous().float(), p_att_feats.contiguous().float()
+            am = att_masks.contiguous().float() if att_masks is not None else None
+            if not att.is_cuda:
+                raise RuntimeError("%s needs device tensors; got a %s tensor (there is no CPU fallback)" % (type(self).__name__, att.device))
+            N, R, H = att.shape[0], att.shape[1], self.rnn_size
+            d = self._dims(N, R)
+            w = _lib.adaatt_weights(self._tensors(), self.num_layers, self.use_bn, self.logit_layers)
+            ws = self._workspace(lib, d, att.device)
+            h_in, c_in = state[0].contiguous().float(), state[1].contiguous().float()
+            logp = torch.empty(N, d.V1, dtype=torch.float32, device=att.device)
+            h, c = torch.empty_like(h_in), torch.empty_like(c_in)
+            check(lib.uic_adaatt_logprobs_state(C.byref(d), C.byref(w), ptr(it.contiguous().long()), ptr(fc), ptr(att), ptr(p_att), ptr(am),
+                                                ptr(h_in), ptr(c_in), ptr(ws), ptr(logp), ptr(h), ptr(c), stream()), "adaatt_logprobs_state")
+        return logp, (h, c)
+
+    def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
+        """AttModel._sample_beam (:167-196) over CaptionModel.beam_search, all images in one device pass; `self.done_beams[k]` is the
+        reference's list for image k (built on first access)."""
+        beam_size = opt.get('beam_size', 10)
+        group_size = opt.get('group_size', 1)
+        if group_size > 1:      # (as AttModel._sample_beam above: the caller only ever receives the best beam of group 0)
+            beam_size = beam_size // group_size
+        if not 1 <= beam_size <= _lib.BEAM_MAX:
+            raise NotImplementedError("beam_size=%r: the MI355X beam kernels hold 1..%d beams" % (beam_size, _lib.BEAM_MAX))
+        assert beam_size <= self.vocab_size + 1
+        with torch.no_grad():
+            lib, d, w, ws, fc, att, am = self._prepare(fc_feats, att_feats, att_masks, beam=int(beam_size))
+            L, n_img, B = self.seq_length, d.N, int(beam_size)
+            seq = torch.zeros(n_img, L, dtype=torch.int64, device=att.device)
+            lp = torch.zeros(n_img, L, dtype=torch.float32, device=att.device)
+            check(lib.uic_adaatt_sample_beam(C.byref(d), C.byref(w), ptr(fc), ptr(att), ptr(am), L, B, int(opt.get('decoding_constraint', 0)),
+                                             int(opt.get('max_ppl', 0)), ptr(ws), ptr(seq), ptr(lp), stream()), "adaatt_sample_beam")
+            cnt = torch.zeros(n_img, dtype=torch.int32, device=att.device)
+            dp = torch.zeros(n_img, L * B, dtype=torch.float32, device=att.device)
+            dseq = torch.zeros(n_img, L * B, L, dtype=torch.int64, device=att.device)
+            dlp = torch.zeros(n_img, L * B, L, dtype=torch.float32, device=att.device)
+            check(lib.uic_adaatt_beam_done_lists(C.byref(d), ptr(ws), L, B, ptr(cnt), ptr(dp), ptr(dseq), ptr(dlp), stream()),
+                  "adaatt_beam_done_lists")
+        self._done_raw = (cnt, dp, dseq, dlp, B)
+        self._done_beams = None
+        return seq, lp
+
+    def _sample(self, fc_feats, attri_feats, att_feats, att_masks=None, opt={}):
+        """P/models/AttModel.py:198-253: (seq, seqLogprobs), both [N, seq_length]."""
+        if self.training:
+            raise NotImplementedError(self._TRAINING % type(self).__name__)
+        if int(opt.get('captions_per_image', 1) or 1) > 1 or opt.get('forced_tokens') is not None:
+            raise NotImplementedError("%s._sample: opt['captions_per_image'] > 1 and opt['forced_tokens'] are extensions of the TopDown "
+                                      "training path" % type(self).__name__)
+        if opt.get('beam_size', 1) > 1:
+            return self._sample_beam(fc_feats, att_feats, att_masks, opt)
+        with torch.no_grad():
+            lib, d, w, ws, fc, att, am = self._prepare(fc_feats, att_feats, att_masks)
+            L = self.seq_length
+            seq = torch.zeros(d.N, L, dtype=torch.int64, device=att.device)
+            lp = torch.zeros(d.N, L, dtype=torch.float32, device=att.device)
+            check(lib.uic_adaatt_sample(C.byref(d), C.byref(w), ptr(fc), ptr(att), ptr(am), L, int(bool(opt.get('sample_max', 1))),
+                                        float(opt.get('temperature', 1.0)), int(opt.get('decoding_constraint', 0)), self.next_seed(), ptr(ws),
+                                        ptr(seq), ptr(lp), stream()), "adaatt_sample")
+        return seq, lp
+
+
+class AdaAttMOModel(AdaAttModel):
+    """AdaAtt with the maxout LSTM (P/models/AttModel.py:663-667)."""
+    use_maxout = True

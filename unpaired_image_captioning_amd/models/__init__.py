@@ -1,6 +1,6 @@
 """`models.setup(opt)` with the reference's dispatch (P/models/__init__.py:22-58), restricted to
 the architectures on the hot path."""
-from .AttModel import TopDownModel  # noqa: F401
+from .AttModel import TopDownModel, AdaAttModel, AdaAttMOModel  # noqa: F401
 from .AttEnsemble import AttEnsemble  # noqa: F401
 from .CaptionModel import CaptionModel  # noqa: F401
 from .FCModel_NMT import FCModel_NMT  # noqa: F401
@@ -23,4 +23,11 @@ def setup(opt):
                                       "and decoding only; training is not built (set i2t_train_flag=0 to load, score and decode a checkpoint)"
                                       % (opt.i2t_train_flag,))
         return TransformerModel(opt)
+    if opt.caption_model in ('adaatt', 'adaattmo'):   # P/models/__init__.py:36-41
+        # evaluation and decoding only, as the transformer
+        if getattr(opt, 'i2t_train_flag', 0):
+            raise NotImplementedError("Caption model not supported by the MI355X hot path: %s with i2t_train_flag=%r -- evaluation "
+                                      "and decoding only; training is not built (set i2t_train_flag=0 to load, score and decode a checkpoint)"
+                                      % (opt.caption_model, opt.i2t_train_flag))
+        return AdaAttModel(opt) if opt.caption_model == 'adaatt' else AdaAttMOModel(opt)
     raise Exception("Caption model not supported by the MI355X hot path: {}".format(opt.caption_model))
