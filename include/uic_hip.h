@@ -172,6 +172,7 @@ typedef struct uic_topdown_batch {
      encoder in front of the captioner (BASELINE configs[4]'s scene-graph GCN, uic_gcn_backward's `dout`): */
   float* d_att_feats;       /* [N, R, D]  ([N / seq_per_img, R, D]); padded regions get zeros.  Needs dims.use_bn == 0 */
   float* d_fc_feats;        /* [N, Dfc]   ([N / seq_per_img, Dfc]) */
+  const int32_t* unfinished_count;   /* optional, see below */
   /* Optional list of the LIVE positions of the batch, for uic_topdown_xe_train_step (live_count NULL = every position is computed, and
      positions with mask 0 contribute exact zeros -- the same result).  A position (t, n) -- decode step t, row n -- is live
      when masks[n, 1 + t] != 0; positions behind a caption's end (LanguageModelCriterion multiplies them by 0,
@@ -190,11 +191,25 @@ typedef struct uic_topdown_batch {
      masked position is harmless.
      Ignored (every position computed) under scheduled sampling, with grad_scale, with logit_layers > 1, without masks, when a row
      of hidden units is not a multiple of 16 bytes, when t_run >
-     UIC_MAX_LIVE_STEPS, or when a count is outside [0, N]. */
+     UIC_MAX_LIVE_STEPS, or when a count is outside [0, N].
+     unfinished_count (declared above the list)  HOST int32 [t_run] or NULL: per decode step t, the number of rows whose caption has
+                   not ended, #{n : 1 + the last t' with masks[n, 1 + t'] != 0  >  t} (masks with holes make it larger than
+                   live_count[t]).  With it (and live_count given, live_rows == NULL), the BPTT loop's two input-gradient GEMMs of a
+                   step run over those rows only wherever they fill fewer 128-row tiles than the batch: an ended row's gradients
+                   are exact zeros, so the loss and every gradient are bit for bit those of the step without the counts.  The
+                   step sizes launches with the counts and checks them on the device against the masks: counts that differ set
+                   rnn_status[0] = UIC_STATUS_UNFINISHED_COUNT | (the first such step) -- the gradients of that call are invalid,
+                   as after a timed-out persistent launch, and no launch leaves its buffers whatever the counts hold.  Ignored
+                   (NULL's path) without rnn_status, in f32, at shapes off the split-K BPTT chain, N > 4096, or a count
+                   outside [0, N]. */
   const int32_t* live_rows;
   const int32_t* live_count;
 } uic_topdown_batch;
 #define UIC_MAX_LIVE_STEPS 64
+#define UIC_STATUS_UNFINISHED_COUNT 0x400u   /* rnn_status[0]: uic_topdown_batch.unfinished_count is not that of the masks */
+/* How many of the last uic_topdown_xe_train_step's input-gradient GEMM launches (two per decode step) ran over the unfinished rows
+ * only (0: no unfinished_count, or every step's rows fill all the tiles). */
+int uic_topdown_compact_launches(int32_t* out);
 
 /* Sizes (bytes) of the two caller-allocated arenas. */
 size_t uic_topdown_workspace_bytes(const uic_topdown_dims* d);
@@ -573,6 +588,12 @@ int uic_linear_f32a(int32_t M, int32_t N, int32_t K, const float* A, int32_t lda
  * attention backward) add the slices while they read them.  One K segment, K % 64 == 0 (bf16) / % 32 (f32). */
 int uic_linear_partials(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* B, int32_t ldb,
                         float* slab, int32_t splitk, void* stream);
+/* ... with the output rows placed by a list (bf16): row i < M of the product is written to row row_map[i] (device int32 [M]) of
+ * slab[z][slab_rows][N], slab_rows >= M; an entry outside [0, slab_rows) drops its row; rows of the slab that no entry names are not
+ * touched.  A is a compact list of the rows that have a result at all: a row's result does not depend on where it sits, so the
+ * rows written are bit for bit those of the unmapped launch over all slab_rows rows.  row_map == NULL: uic_linear_partials. */
+int uic_linear_partials_rows(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* B, int32_t ldb,
+                             float* slab, int32_t splitk, const int32_t* row_map, int32_t slab_rows, void* stream);
 
 /* Weight gradient of nn.Linear without transposed copies: dW[M,N] (f32) = dY[K,M]^T X[K,N] (+= if accumulate), dY / X bf16
  * row-major with the reduction index (caption rows / decode steps) as the ROW index, exactly as the backward pass holds
@@ -645,6 +666,32 @@ int uic_h2att_cell_bwd(int32_t dtype, int32_t N, int32_t H, int32_t A, const voi
                        const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
                        const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
                        float* dc, const void* gates, const float* c_prev, const float* c, void* dgates, void* stream);
+/* The two cell-backward launches of a BPTT step whose d x GEMMs run over the unfinished captions only (uic_topdown_batch.
+ * unfinished_count).  row_len (device int32 [M]): every row's caption length; step: the decode step t of the call; rank (device
+ * int32 [M]) and dgates_c ([M, 4H] bf16, optional): a row with row_len > t stores its dgates row at row rank[m] of dgates_c too.
+ * Slab rows of ended captions were not written and may hold anything: they are dropped by a select, never multiplied.
+ *   uic_lstm_cell_bwd_live (the lang_lstm cell; dh0 and c_prev present, bf16, the UIC_LSTM_BWD_VEC4 conditions): both slabs are step
+ *     t + 1's -- zeros for row_len <= t + 1; a row with row_len <= t writes a zero dgates row and leaves, d c untouched.
+ *   uic_h2att_cell_bwd_live: slabA is step t's own d x2 -- zeros for row_len <= t --, slabB step t + 1's d x1 -- zeros for
+ *     row_len <= t + 1.
+ * row_len == NULL: uic_lstm_cell_bwd_sources / uic_h2att_cell_bwd. */
+int uic_lstm_cell_bwd_live(int32_t M, int32_t H, const float* dh0, int32_t lddh0, float drop_p, uint32_t seed, uint32_t site,
+                           const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                           const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                           float* dc, const void* gates, const float* c_prev, const float* c, void* dgates,
+                           const int32_t* row_len, const int32_t* rank, int32_t step, void* dgates_c, void* stream);
+int uic_h2att_cell_bwd_live(int32_t N, int32_t H, int32_t A, const void* datth, const void* h2attT,
+                            const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                            const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                            float* dc, const void* gates, const float* c_prev, const float* c, void* dgates,
+                            const int32_t* row_len, const int32_t* rank, int32_t step, void* dgates_c, void* stream);
+/* The rows of a batch by caption length (csrc/live_rows.hip): masks [N, ld] f32 on the device, decode step t in column col0 + t,
+ * t < T <= UIC_MAX_LIVE_STEPS, N <= 4096.  row_len[n] = 1 + the last t with a non-zero mask (0: none); order [N] = the rows sorted by
+ * row_len, longest first, equal lengths in ascending row order (no atomics: the same masks give the same order); rank [N] its
+ * inverse; unfinished [T + 1], unfinished[t] = #{n : row_len[n] > t} -- the rows order[0 .. unfinished[t]).  expect (HOST int32 [T],
+ * optional) and status (device uint32, optional): where expect[t] != unfinished[t], status[0] = UIC_STATUS_UNFINISHED_COUNT | t. */
+int uic_live_order(const float* masks, int32_t ld, int32_t col0, int32_t N, int32_t T, int32_t* row_len, int32_t* order, int32_t* rank,
+                   int32_t* unfinished, const int32_t* expect, uint32_t* status, void* stream);
 
 /* Attention.forward after h2att (P/models/AttModel.py:544-556) and its backward, split into the part inside the BPTT loop (step) and
  * the sums over the decode steps behind it (accum); csrc/attention.hip.  p_att [N,R,A], att [N,R,H], ctx and d_att_h in `dtype`

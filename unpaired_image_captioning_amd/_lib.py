@@ -378,7 +378,7 @@ class Batch(C.Structure):
                 ("labels", C.c_void_p), ("ld_labels", C.c_int32),
                 ("masks", C.c_void_p), ("ld_masks", C.c_int32),
                 ("grad_scale", C.c_void_p), ("ld_grad_scale", C.c_int32), ("ss_prob", C.c_float),
-                ("d_att_feats", C.c_void_p), ("d_fc_feats", C.c_void_p),
+                ("d_att_feats", C.c_void_p), ("d_fc_feats", C.c_void_p), ("unfinished_count", C.POINTER(C.c_int32)),
                 ("live_rows", C.c_void_p), ("live_count", C.POINTER(C.c_int32))]
 
 
@@ -470,6 +470,16 @@ _SIGS = {
     "uic_linear_f32a": (C.c_int, [C.c_int32] * 3 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                    C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "uic_linear_partials": (C.c_int, [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "uic_linear_partials_rows": (C.c_int, [C.c_int32] * 4 + [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_void_p]),
+    "uic_lstm_cell_bwd_live": (C.c_int, [C.c_int32] * 2 + [C.c_void_p, C.c_int32, C.c_float, C.c_uint32, C.c_uint32] +
+                               [C.c_void_p, C.c_int32, C.c_int32, C.c_size_t] * 2 + [C.c_void_p] * 5 +
+                               [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "uic_h2att_cell_bwd_live": (C.c_int, [C.c_int32] * 3 + [C.c_void_p] * 2 + [C.c_void_p, C.c_int32, C.c_int32, C.c_size_t] * 2 +
+                                [C.c_void_p] * 5 + [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "uic_live_order": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32] + [C.c_void_p] * 4 +
+                       [C.POINTER(C.c_int32), C.c_void_p, C.c_void_p]),
+    "uic_topdown_compact_launches": (C.c_int, [C.POINTER(C.c_int32)]),
     "uic_ciderd_table_slots": (C.c_int64, [C.c_int64]),
     "uic_ciderd_table_build": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64]),
     "uic_ciderd_scores": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
@@ -607,9 +617,18 @@ def load():
 _status = {}
 
 
+STATUS_UNFINISHED_COUNT = 0x400                 # UIC_STATUS_UNFINISHED_COUNT
+
+
 class PersistentTimeout(RuntimeError):
     """A bounded spin of a persistent recurrence kernel gave up (another process on the GPU, a long kernel on another stream):
     the results of that call are invalid and the optimizer step that followed was skipped on the device."""
+
+
+class UnfinishedCountMismatch(PersistentTimeout):
+    """uic_topdown_batch.unfinished_count was not that of the batch's masks (the step checks it on the device): the gradients of that
+    call are invalid and the optimizer step that followed was skipped on the device -- handled like a timed-out step (Trainer rolls
+    its step counter back), hence the base class."""
 
 
 def status_words(device=None):
@@ -625,13 +644,17 @@ def status_words(device=None):
 
 def persistent_status(device=None):
     """[timeout code, XCD-local launches, SAFE launches] of the persistent recurrence kernels on `device`; synchronises.
-    A non-zero timeout code raises (and is cleared)."""
+    A non-zero timeout code raises (and is cleared); so does the code of a wrong uic_topdown_batch.unfinished_count
+    (UnfinishedCountMismatch)."""
     dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     status_words(dev)
     vals = [int(v) for v in _status[idx].cpu().tolist()]
     if vals[0] != 0:
         _status[idx].zero_()
+        if vals[0] & ~0xff == STATUS_UNFINISHED_COUNT:
+            raise UnfinishedCountMismatch("unfinished_count[%d] is not the number of rows whose caption is unfinished at that decode "
+                                          "step: the gradients of the last step are invalid" % (vals[0] & 0xff))
         raise PersistentTimeout("persistent recurrence kernel timed out (code 0x%x): results of the last calls are invalid" % vals[0])
     return vals[:3]
 

@@ -118,6 +118,20 @@ int uic_linear_partials(int32_t dtype, int32_t M, int32_t N, int32_t K, const vo
   return uic_gemm_launch(g, (hipStream_t)stream);
 }
 
+int uic_linear_partials_rows(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* A, int32_t lda, const void* B, int32_t ldb,
+                             float* slab, int32_t splitk, const int32_t* row_map, int32_t slab_rows, void* stream) {
+  if (!row_map) return uic_linear_partials(dtype, M, N, K, A, lda, B, ldb, slab, splitk, stream);
+  UIC_REQUIRE(slab && splitk >= 1 && splitk <= 16, "linear_partials_rows: slab / splitk=%d", splitk);
+  UIC_REQUIRE(uic_gemm_glds_eligible(dtype, K), "linear_partials_rows: K=%d must be a multiple of one 128-byte round", K);
+  UIC_REQUIRE(M >= 1 && slab_rows >= M, "linear_partials_rows: M=%d must be in [1, slab_rows=%d]", M, slab_rows);
+  UicGemmParams g;
+  memset(&g, 0, sizeof(g));
+  g.dtype = dtype; g.M = M; g.N = N; g.nseg = 1;
+  g.seg[0].A = A; g.seg[0].B = B; g.seg[0].K = K; g.seg[0].lda = lda; g.seg[0].ldb = ldb;
+  g.slab = slab; g.splitk = splitk; g.slab_row_map = row_map; g.slab_rows = slab_rows;
+  return uic_gemm_launch(g, (hipStream_t)stream);
+}
+
 int uic_linear_wgrad(int32_t dtype, int32_t M, int32_t N, int32_t K, const void* dY, int32_t ldy, const void* X, int32_t ldx,
                      float* dW, int32_t ldw, void* workspace, size_t workspace_bytes, int32_t accumulate, void* stream) {
   UIC_REQUIRE(dY && X && dW && workspace, "linear_wgrad: null pointer");
@@ -199,6 +213,46 @@ int uic_h2att_cell_bwd(int32_t dtype, int32_t N, int32_t H, int32_t A, const voi
   p.slabB = slabB; p.ldB = ldB; p.nB = nB; p.strideB = strideB;
   p.dc = dc; p.gates = gates; p.c_prev = c_prev; p.c = c; p.dgates = dgates;
   return uic_h2att_cell_bwd_launch(p, (hipStream_t)stream);
+}
+
+int uic_lstm_cell_bwd_live(int32_t M, int32_t H, const float* dh0, int32_t lddh0, float drop_p, uint32_t seed, uint32_t site,
+                           const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                           const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                           float* dc, const void* gates, const float* c_prev, const float* c, void* dgates,
+                           const int32_t* row_len, const int32_t* rank, int32_t step, void* dgates_c, void* stream) {
+  UicLstmBwdParams p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = UIC_BF16; p.M = M; p.H = H;
+  p.dh0 = dh0; p.lddh0 = lddh0; p.drop_p = drop_p; p.seed = seed; p.site = site;
+  p.slabA = slabA; p.ldA = ldA; p.nA = nA; p.strideA = strideA;
+  p.slabB = slabB; p.ldB = ldB; p.nB = nB; p.strideB = strideB;
+  p.dc = dc; p.gates = gates; p.c_prev = c_prev; p.c = c; p.dgates = dgates;
+  p.row_len = row_len; p.rank = rank; p.step = step; p.dgates_c = dgates_c;
+  return uic_lstm_bwd_launch(p, (hipStream_t)stream);
+}
+
+int uic_h2att_cell_bwd_live(int32_t N, int32_t H, int32_t A, const void* datth, const void* h2attT,
+                            const float* slabA, int32_t ldA, int32_t nA, size_t strideA,
+                            const float* slabB, int32_t ldB, int32_t nB, size_t strideB,
+                            float* dc, const void* gates, const float* c_prev, const float* c, void* dgates,
+                            const int32_t* row_len, const int32_t* rank, int32_t step, void* dgates_c, void* stream) {
+  UicH2attCellParams p;
+  memset(&p, 0, sizeof(p));
+  p.dtype = UIC_BF16; p.N = N; p.H = H; p.A = A; p.datth = datth; p.h2attT = h2attT;
+  p.slabA = slabA; p.ldA = ldA; p.nA = nA; p.strideA = strideA;
+  p.slabB = slabB; p.ldB = ldB; p.nB = nB; p.strideB = strideB;
+  p.dc = dc; p.gates = gates; p.c_prev = c_prev; p.c = c; p.dgates = dgates;
+  p.row_len = row_len; p.rank = rank; p.step = step; p.dgates_c = dgates_c;
+  return uic_h2att_cell_bwd_launch(p, (hipStream_t)stream);
+}
+
+int uic_live_order(const float* masks, int32_t ld, int32_t col0, int32_t N, int32_t T, int32_t* row_len, int32_t* order, int32_t* rank,
+                   int32_t* unfinished, const int32_t* expect, uint32_t* status, void* stream) {
+  UIC_REQUIRE(masks && row_len && order && rank && unfinished && ld >= col0 + T && col0 >= 0, "live_order: null pointer or ld=%d < col0 + T", ld);
+  UIC_REQUIRE(uic_live_order_ok(N, T), "live_order: N=%d outside [1, 4096] or T=%d outside [1, %d]", N, T, UIC_MAX_LIVE_STEPS);
+  const UicLiveOrder ord{order, rank, unfinished, expect, status};
+  // (the list itself is not wanted: out_len = 0 writes nothing through `out`)
+  return uic_live_list_launch(masks, ld, col0, N, T * N, order, 0, (hipStream_t)stream, nullptr, nullptr, 0, row_len, &ord);
 }
 
 int uic_attention_fwd_strided(int32_t dtype, int32_t N, int32_t R, int32_t A, int32_t H, const float* att_h, const void* p_att,

@@ -22,7 +22,10 @@ __device__ __forceinline__ f32x4 mma16(const u32x4f& a, const u32x4f& b, f32x4 c
   return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
 }
 
-template <int KS>     // k-steps (32 K elements) per wave: A = 4 waves x KS x 32
+// LIVE (UicH2attCellParams.row_len): the thread's row brings its caption length and rank with the burst below, used behind the GEMM
+// only: a slab whose GEMM ran over the unfinished rows alone has no words for the others -- what lies there may be anything, so
+// such a row takes zeros by a select --, and a row that is unfinished at this step stores its result a second time, compactly.
+template <int KS, bool LIVE = false>     // k-steps (32 K elements) per wave: A = 4 waves x KS x 32
 __global__ __launch_bounds__(256) void h2att_cell_bwd_kernel(const UicH2attCellParams p) {
   __shared__ __attribute__((aligned(16))) float red[4][FT * FT];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, lq = lane >> 4;
@@ -66,6 +69,8 @@ __global__ __launch_bounds__(256) void h2att_cell_bwd_kernel(const UicH2attCellP
   const float4 c4 = *(const float4*)(p.c + idx);
   const float4 cp4r = *(const float4*)((p.c_prev ? p.c_prev : standin) + idx);
   const float4 dc4 = *(const float4*)(p.dc + idx);
+  int len = 0x7fffffff, rk = 0;
+  if constexpr (LIVE) { len = p.row_len[rr]; rk = p.rank[rr]; }
   float4 sv[8];
   {
     const float* bA = p.nA ? p.slabA : standin;
@@ -111,7 +116,9 @@ __global__ __launch_bounds__(256) void h2att_cell_bwd_kernel(const UicH2attCellP
     float4 ds = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
     for (int z = 0; z < 8; ++z) {
-      const bool use = z < 4 ? z < p.nA : z - 4 < p.nB;
+      // (LIVE: slabA is this step's d x2, unwritten for a row that ended before the step; slabB the next step's d x1, unwritten
+      // for a row that ends with this step or before)
+      const bool use = z < 4 ? z < p.nA && len > p.step : z - 4 < p.nB && len > p.step + 1;
       ds.x += use ? sv[z].x : 0.f; ds.y += use ? sv[z].y : 0.f; ds.z += use ? sv[z].z : 0.f; ds.w += use ? sv[z].w : 0.f;
     }
     dh[0] = s.x + ds.x; dh[1] = s.y + ds.y; dh[2] = s.z + ds.z; dh[3] = s.w + ds.w;
@@ -141,6 +148,15 @@ __global__ __launch_bounds__(256) void h2att_cell_bwd_kernel(const UicH2attCellP
   bf16_t* D = (bf16_t*)p.dgates + (size_t)crow * 4 * H + cu;
 #pragma unroll
   for (int q = 0; q < 4; ++q) *(uint2*)(D + q * H) = make_uint2(uic_pack_bf16x2(o4[q][0], o4[q][1]), uic_pack_bf16x2(o4[q][2], o4[q][3]));
+  if constexpr (LIVE) {
+    if (p.dgates_c && len > p.step) {
+      bf16_t* Dc = (bf16_t*)p.dgates_c + (size_t)rk * 4 * H + cu;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *(uint2*)(Dc + q * H) = make_uint2(uic_pack_bf16x2(o4[q][0], o4[q][1]), uic_pack_bf16x2(o4[q][2], o4[q][3]));
+    }
+  }
+  // (a row that has not begun -- row_len <= step -- has d att_h = 0 from the attention backward's exit and zeros for both slabs:
+  // d h = 0, so the d c it carries, cleared at the loop's start, stays zero)
   *(float4*)(p.dc + idx) = make_float4(dcn[0], dcn[1], dcn[2], dcn[3]);
 }
 
@@ -163,7 +179,18 @@ int uic_h2att_cell_bwd_launch(const UicH2attCellParams& p, hipStream_t s) {
               "h2att_cell_bwd: slab sources");
   if (p.N == 0) return UIC_OK;
   UIC_REQUIRE(uic_h2att_cell_bwd_eligible(p), "h2att_cell_bwd: shape not eligible (bf16, H %% 32 == 0, A in {128, 256, 512})");
+  UIC_REQUIRE(p.row_len ? p.rank && p.step >= 0 && ((uintptr_t)p.dgates_c & 7) == 0 : !p.rank && !p.dgates_c,
+              "h2att_cell_bwd: row_len, rank and step >= 0 come together (dgates_c optional, 8-byte aligned)");
   const dim3 grid((unsigned)((p.N + FT - 1) / FT), (unsigned)(p.H / FT));
+  if (p.row_len) {
+    switch (p.A / 128) {
+      case 1: hipLaunchKernelGGL((h2att_cell_bwd_kernel<1, true>), grid, dim3(256), 0, s, p); break;
+      case 2: hipLaunchKernelGGL((h2att_cell_bwd_kernel<2, true>), grid, dim3(256), 0, s, p); break;
+      default: hipLaunchKernelGGL((h2att_cell_bwd_kernel<4, true>), grid, dim3(256), 0, s, p); break;
+    }
+    UIC_LAUNCH_CHECK("h2att_cell_bwd_kernel (row_len)");
+    return UIC_OK;
+  }
   switch (p.A / 128) {
     case 1: hipLaunchKernelGGL(h2att_cell_bwd_kernel<1>, grid, dim3(256), 0, s, p); break;
     case 2: hipLaunchKernelGGL(h2att_cell_bwd_kernel<2>, grid, dim3(256), 0, s, p); break;

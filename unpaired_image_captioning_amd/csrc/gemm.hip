@@ -438,7 +438,11 @@ __global__ __launch_bounds__(64 * WM * WN * KS) void uic_gemm_kernel(const UicGe
 // -- one L2 / Infinity Cache latency (~0.8 us) per 64-deep K round whatever the MFMA time (0.2 us), hidden only by the CU's second
 // workgroup; 3 = a ring of three buffers (96 KB: one workgroup per CU), two rounds in flight.  For launches that put at most one
 // workgroup on a CU anyway -- the BPTT loop's split-K d x GEMMs: 160 / 240 workgroups of 8 rounds -- the ring is what hides the latency.
-template <typename T, int STAGES = 2>
+// MAPPED (UicGemmParams.slab_row_map, split-K slabs only): the map entries of the tile's rows are requested before the first K round
+// and used in the epilogue only -- nothing is loaded between the K loop and the stores.  (First form: every lane requested the 32
+// entries of the rows it holds, 32 loads in front of the first LDS-DMA round: + 1 us per launch, which made the compact d x1 launch
+// slower than the full one, 10.5 against 9.5 us.)
+template <typename T, int STAGES = 2, bool MAPPED = false>
 __global__ __launch_bounds__(256, 2) void uic_gemm_glds_kernel(const UicGemmParams p) {   // (2 waves per SIMD = two workgroups per CU: <= 256 registers)
   constexpr int BM = 128, BN = 128;
   constexpr int BK = 128 / (int)sizeof(T);
@@ -474,6 +478,15 @@ __global__ __launch_bounds__(256, 2) void uic_gemm_glds_kernel(const UicGemmPara
     bn = rem / gsz;
   }
   const int m0 = bm * BM, n0 = bn * BN;
+
+  // MAPPED: a wave's output rows are the 64 rows m0 + 64 wm ...: ONE request per lane, for the row of its own number (clamped to
+  // the last row, dropped below by a select: not a load under a condition); the epilogue hands the entries round by lane shuffles
+  int mval = -1;
+  if constexpr (MAPPED) {
+    const int row = m0 + wm * 64 + lane;
+    const int v = p.slab_row_map[min(row, p.M - 1)];
+    mval = row < p.M ? v : -1;
+  }
 
   const UicGemmSeg sg = p.seg[0];
   // per-lane source pointers of this wave's 4 A and 4 B LDS-DMA instructions per round
@@ -608,6 +621,27 @@ __global__ __launch_bounds__(256, 2) void uic_gemm_glds_kernel(const UicGemmPara
     }
   }
 
+  if constexpr (MAPPED) {   // raw partial tile -> rows slab_row_map[row] of slab[z] (32-bit offsets: the launcher checked the size)
+    float* slab = p.slab + (size_t)bz * p.slab_rows * p.N;
+    int mrow[2][16];                     // the slab row of every output row this lane holds (every lane takes part: no test before)
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) mrow[i][reg] = __shfl(mval, i * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half);
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int col = n0 + (wn * 2 + j) * 32 + r32;
+        if (col >= p.N) continue;
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+          const int mr = mrow[i][reg];
+          if ((unsigned)mr < (unsigned)p.slab_rows) slab[(unsigned)mr * (unsigned)p.N + (unsigned)col] = acc[i][j][reg];
+        }
+      }
+    return;
+  }
   if (p.slab) {   // raw partial tile -> slab[z]
     float* slab = p.slab + (size_t)bz * p.M * p.N;
     if (m0 + BM <= p.M && n0 + BN <= p.N && (size_t)p.M * (size_t)p.N < ((size_t)1 << 31)) {   // whole tile: no tests, 32-bit offsets
@@ -762,6 +796,22 @@ int launch_glds(const UicGemmParams& p, hipStream_t s) {
   const int rounds = p.seg[0].K / (128 / (int)sizeof(T)) / (p.splitk > 1 ? p.splitk : 1);
   const long wgs = (long)grid.x * grid.y * grid.z;
   const bool ring = ((wgs <= 192 && rounds >= 3) || (wgs <= 256 && rounds >= 32)) && !(p.flags & UIC_GEMM_NO_RING);   // (long K loops: also at one workgroup per CU)
+  if (p.slab_row_map) {
+    if constexpr (sizeof(T) == 2) {
+      static bool configured_map = false;
+      if (!configured_map) {
+        UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)uic_gemm_glds_kernel<T, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 65536),
+                              "hipFuncSetAttribute(gemm glds, row map)"));
+        UIC_TRY(uic_check_hip(hipFuncSetAttribute((const void*)uic_gemm_glds_kernel<T, 3, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 98304),
+                              "hipFuncSetAttribute(gemm glds ring, row map)"));
+        configured_map = true;
+      }
+      if (ring) hipLaunchKernelGGL((uic_gemm_glds_kernel<T, 3, true>), grid, dim3(256), 98304, s, p);
+      else hipLaunchKernelGGL((uic_gemm_glds_kernel<T, 2, true>), grid, dim3(256), 65536, s, p);
+      UIC_LAUNCH_CHECK("uic_gemm_glds_kernel (row map)");
+      return UIC_OK;
+    }
+  }
   if (ring) hipLaunchKernelGGL((uic_gemm_glds_kernel<T, 3>), grid, dim3(256), 98304, s, p);
   else hipLaunchKernelGGL((uic_gemm_glds_kernel<T, 2>), grid, dim3(256), 65536, s, p);
   UIC_LAUNCH_CHECK("uic_gemm_glds_kernel");
@@ -830,9 +880,11 @@ int launch_typed(const UicGemmParams& p, hipStream_t s) {
   if (p.flags & UIC_GEMM_FORCE_256) return uic_gemm_pp_launch(p, 256, s);
   if (p.flags & UIC_GEMM_FORCE_192) return uic_gemm_pp_launch(p, 192, s);
   if (p.flags & UIC_GEMM_FORCE_PP128) return uic_gemm_pp_launch(p, 128, s);
-  if (!(p.flags & UIC_GEMM_FORCE_128) && uic_gemm_pp_wins(p)) return uic_gemm_pp_launch(p, 0, s);
+  if (!(p.flags & UIC_GEMM_FORCE_128) && !p.slab_row_map && uic_gemm_pp_wins(p)) return uic_gemm_pp_launch(p, 0, s);
   if (p.slab) {
     UIC_REQUIRE(glds_ok && !p.lstm, "gemm: slab output needs one K segment that is a multiple of 128 bytes");
+    UIC_REQUIRE(!p.slab_row_map || (sizeof(T) == 2 && p.slab_rows >= p.M && (size_t)p.slab_rows * (size_t)p.N < ((size_t)1 << 31)),
+                "gemm: slab_row_map needs bf16, slab_rows=%d >= M=%d and a slab slice below 2^31 elements", p.slab_rows, p.M);
     return launch_glds<T>(p, s);
   }
   if (blocks128 >= 200 && glds_ok && !p.C_pre) return launch_glds<T>(p, s);

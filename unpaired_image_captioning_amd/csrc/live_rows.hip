@@ -3,6 +3,8 @@
 // (the position-indexed operands of the step run over the listed rows only).
 #include "uic_common.h"
 #include "uic_host.h"
+#include "../../include/uic_hip.h"
+#include <string.h>
 
 namespace {
 
@@ -16,13 +18,68 @@ __device__ inline void live_row_len(const float* __restrict__ mask, int ld, int 
     row_len[n] = len;
   }
 }
+// The rows ordered by their length, longest first (UicLiveOrder, uic_common.h): a stable counting sort with the T + 1 lengths as
+// buckets, in the list kernels' own workgroup behind live_row_len.  Wave w of the row space (rows 64 w ... 64 w + 63) counts its rows
+// of every length with one ballot each; the counts meet in LDS as cnt[(T - len) * W + w] -- the order of the sorted output --, one
+// wave scans them, and a row's place is its (length, wave) offset + the rows of that length below it in its wave.  No atomics: the
+// same lengths give the same order.  unfinished[t] = the offset of bucket t = the number of rows with a greater length.
+constexpr int LO_MAX_WAVES = 64;                       // rows / 64 the order covers (uic_live_order_ok)
+constexpr int LO_MAX_ENT = LO_MAX_WAVES * (UIC_MAX_LIVE_STEPS + 1);
+struct LiveOrderArgs {
+  int* order; int* rank; int* unfinished; unsigned* status;
+  int has_expect;
+  int expect[UIC_MAX_LIVE_STEPS];
+};
+__device__ inline void live_order(const int* __restrict__ row_len, int N, int T, const LiveOrderArgs& o, int* s_ent, int tid) {
+  const int lane = tid & 63, wave = tid >> 6;
+  const int W = (N + 63) >> 6, E = (T + 1) * W;
+  __syncthreads();                                     // (row_len was written by this workgroup)
+  for (int w = wave; w < W; w += 16) {
+    const int n = w * 64 + lane;
+    const int len = n < N ? row_len[n] : -1;
+    for (int v = 0; v <= T; ++v) {
+      const unsigned long long b = __ballot(len == v);
+      if (lane == 0) s_ent[(T - v) * W + w] = __popcll(b);
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {                                     // exclusive prefix of the E counts, in place: a run per lane + a wave scan
+    const int per = (E + 63) >> 6, e0 = lane * per, e1 = min(E, e0 + per);
+    int sum = 0;
+    for (int e = e0; e < e1; ++e) sum += s_ent[e];
+    int incl = sum;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) { const int up = __shfl_up(incl, d); if (lane >= d) incl += up; }
+    int run = incl - sum;
+    for (int e = e0; e < e1; ++e) { const int c = s_ent[e]; s_ent[e] = run; run += c; }
+  }
+  __syncthreads();
+  for (int w = wave; w < W; w += 16) {
+    const int n = w * 64 + lane;
+    const int len = n < N ? row_len[n] : -1;
+    int at = 0;
+    for (int v = 0; v <= T; ++v) {
+      const unsigned long long b = __ballot(len == v);
+      if (len == v) at = s_ent[(T - v) * W + w] + __popcll(b & ((1ull << lane) - 1ull));
+    }
+    if (n < N) { o.rank[n] = at; o.order[at] = n; }
+  }
+  // unfinished[t] = #{n : row_len[n] > t} (unfinished[T] = 0); against the counts the caller sized its launches with
+  if (tid <= T) o.unfinished[tid] = tid < T ? s_ent[(T - tid) * W] : 0;
+  if (tid == 0 && o.has_expect && o.status) {
+    for (int t = 0; t < T; ++t)
+      if (o.expect[t] != s_ent[(T - t) * W]) { o.status[0] = (unsigned)UIC_STATUS_UNFINISHED_COUNT | (unsigned)t; break; }
+  }
+}
+
 // out = the positions p = t * N + n, ascending, whose mask[n * ld + col0 + t] is not zero; entries behind them up to out_len: -1.
 // ONE workgroup: an ordered compaction of ~1e4 positions in chunks of 1024 (ballot + wave prefix + one running offset), a few
 // microseconds beside the prologue -- the list never crosses PCIe.
 // inv (optional, [M]): the inverse -- inv[p] = the list index of position p, or -1; zero16 (optional): n16 16-byte words cleared on
 // the way (the padding rows of the compact operand the list's consumer fills by itself, rnn_persist.hip)
 __global__ __launch_bounds__(1024) void live_list_kernel(const float* __restrict__ mask, int ld, int col0, int N, int M, int* __restrict__ out, int out_len,
-                                                         int* __restrict__ inv, uint4* __restrict__ zero16, int n16, int* __restrict__ row_len) {
+                                                         int* __restrict__ inv, uint4* __restrict__ zero16, int n16, int* __restrict__ row_len, const LiveOrderArgs ord) {
+  __shared__ int s_ent[LO_MAX_ENT];
   __shared__ int s_wave[16];
   __shared__ int s_base;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -50,13 +107,15 @@ __global__ __launch_bounds__(1024) void live_list_kernel(const float* __restrict
   for (int i = s_base + tid; i < out_len; i += 1024) out[i] = -1;
   for (int i = tid; i < n16; i += 1024) zero16[i] = make_uint4(0u, 0u, 0u, 0u);
   if (row_len) live_row_len(mask, ld, col0, N, M / N, row_len, tid);
+  if (ord.order) live_order(row_len, N, M / N, ord, s_ent, tid);       // (uniform: a kernel argument)
 }
 // the same for M <= 16 x 1024 positions (the captioner's 10 880, the NMT step's ~2 000) with ONE round trip to memory: every
 // thread requests its <= 16 mask words at once, the per-(round, wave) counts meet in LDS, one wave scans the 256 of them
 // (19 -> 4 us: the first form paid a memory latency and three barriers per 1024 positions)
 constexpr int LL_R = 16;
 __global__ __launch_bounds__(1024) void live_list_burst_kernel(const float* __restrict__ mask, int ld, int col0, int N, int M, int* __restrict__ out, int out_len,
-                                                               int* __restrict__ inv, uint4* __restrict__ zero16, int n16, int* __restrict__ row_len) {
+                                                               int* __restrict__ inv, uint4* __restrict__ zero16, int n16, int* __restrict__ row_len, const LiveOrderArgs ord) {
+  __shared__ int s_ent[LO_MAX_ENT];
   __shared__ int s_cnt[LL_R * 16];
   __shared__ int s_off[LL_R * 16 + 1];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -101,6 +160,7 @@ __global__ __launch_bounds__(1024) void live_list_burst_kernel(const float* __re
   for (int i = s_off[LL_R * 16] + tid; i < out_len; i += 1024) out[i] = -1;
   for (int i = tid; i < n16; i += 1024) zero16[i] = make_uint4(0u, 0u, 0u, 0u);
   if (row_len) live_row_len(mask, ld, col0, N, M / N, row_len, tid);
+  if (ord.order) live_order(row_len, N, M / N, ord, s_ent, tid);       // (uniform: a kernel argument)
 }
 
 // out[m, :] = src[map[m], :] (rows of `chunks` 16-byte pieces) for m < M; rows [M, Mpad) of out are cleared
@@ -125,14 +185,25 @@ __global__ __launch_bounds__(256) void scatter_rows_kernel(const uint4* __restri
 
 }  // namespace
 
+bool uic_live_order_ok(int N, int T) { return N >= 1 && N <= 64 * LO_MAX_WAVES && T >= 1 && T <= UIC_MAX_LIVE_STEPS; }
 int uic_live_list_launch(const float* mask, int ld, int col0, int N, int M, int* out, int out_len, hipStream_t s, int* inv, void* zero, size_t zero_bytes,
-                         int* row_len) {
+                         int* row_len, const UicLiveOrder* order) {
   UIC_REQUIRE(mask && out && N > 0 && M >= 0 && out_len >= 0, "live_list: bad arguments");
+  LiveOrderArgs ord;
+  memset(&ord, 0, sizeof(ord));
+  if (order) {
+    UIC_REQUIRE(row_len && order->order && order->rank && order->unfinished && M % N == 0 && uic_live_order_ok(N, M / N),
+                "live_list: the row order needs row_len and its three outputs, N=%d <= %d rows and M / N = %d <= %d steps", N,
+                64 * LO_MAX_WAVES, M / N, UIC_MAX_LIVE_STEPS);
+    ord.order = order->order; ord.rank = order->rank; ord.unfinished = order->unfinished; ord.status = order->status;
+    ord.has_expect = order->expect != nullptr;
+    if (order->expect) memcpy(ord.expect, order->expect, (size_t)(M / N) * sizeof(int));
+  }
   UIC_REQUIRE(zero_bytes == 0 || (zero && ((uintptr_t)zero & 15) == 0 && zero_bytes % 16 == 0 && zero_bytes < ((size_t)1 << 30)), "live_list: the cleared region must be 16-byte aligned / sized");
   if (out_len == 0 && !inv && !row_len) return UIC_OK;
   const int n16 = (int)(zero_bytes / 16);
-  if (M <= LL_R * 1024 && M > 0) hipLaunchKernelGGL(live_list_burst_kernel, dim3(1), dim3(1024), 0, s, mask, ld, col0, N, M, out, out_len, inv, (uint4*)zero, n16, row_len);
-  else hipLaunchKernelGGL(live_list_kernel, dim3(1), dim3(1024), 0, s, mask, ld, col0, N, M, out, out_len, inv, (uint4*)zero, n16, row_len);
+  if (M <= LL_R * 1024 && M > 0) hipLaunchKernelGGL(live_list_burst_kernel, dim3(1), dim3(1024), 0, s, mask, ld, col0, N, M, out, out_len, inv, (uint4*)zero, n16, row_len, ord);
+  else hipLaunchKernelGGL(live_list_kernel, dim3(1), dim3(1024), 0, s, mask, ld, col0, N, M, out, out_len, inv, (uint4*)zero, n16, row_len, ord);
   UIC_LAUNCH_CHECK("live_list");
   return UIC_OK;
 }

@@ -50,13 +50,19 @@ __global__ void lstm_bwd_kernel(const UicLstmBwdParams p) {
 // latency and instruction issue, not of bytes (captioner step 3.775 -> 3.757 ms over six alternations).  Same formulas per element.
 // SIMPLE: dh0 and c_prev present, dh1 / dh2 absent -- the two calls of the split BPTT chain (topdown_step.hip); then no load has an
 // optional address at all, only the slab stand-ins below.
-template <typename T, bool SIMPLE>
+// LIVE (SIMPLE only; UicLstmBwdParams.row_len): the row's caption length and rank are requested with the operands -- the row is the
+// workgroup's, so they are two scalar loads -- and decide, uniformly per workgroup: a row that ended at or before this step writes
+// its zero row and leaves; a row whose last step this is drops both slab sums by a select (its slab rows were not written this
+// time: the words there may be anything, NaN included -- never a multiply); every other row stores its result twice.
+template <typename T, bool SIMPLE, bool LIVE = false>
 __global__ __launch_bounds__(NT) void lstm_bwd_vec4_kernel(const UicLstmBwdParams p) {
   const int H = p.H, H4 = H >> 2;
   const int m = blockIdx.y, u4 = blockIdx.x * blockDim.x + threadIdx.x;      // (row from the grid: no division per lane)
   if (u4 >= H4) return;
   const int u = u4 * 4;
   const size_t idx = (size_t)m * H + u;
+  int len = 0x7fffffff, rk = 0;
+  if constexpr (LIVE) { len = p.row_len[m]; rk = p.rank ? p.rank[m] : 0; }
   const float inv_keep = p.drop_p > 0.f ? 1.f / (1.f - p.drop_p) : 1.f;
   // Every load first, and NONE behind a run-time condition (round 6): an optional source that is absent is read from a valid
   // stand-in address (the d c row) and dropped by a select below.  hipcc waits for a predicated load at the join of its branch --
@@ -92,6 +98,20 @@ __global__ __launch_bounds__(NT) void lstm_bwd_vec4_kernel(const UicLstmBwdParam
 #pragma unroll
     for (int z = 0; z < 4; ++z) sv[4 + z] = ld4(bB, (size_t)min(z, mB) * sB + oB);
   }
+  if constexpr (LIVE) {
+    if (len <= p.step) {
+      // the caption ended before this step: d h, the carried d c (cleared at the loop's start, never written by a row that has not
+      // begun: this exit is what keeps it so) and with them the whole row are zero
+      T* Z = (T*)p.dgates + (size_t)m * 4 * H + u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        if constexpr (sizeof(T) == 2) *(uint2*)(Z + q * H) = make_uint2(0u, 0u);
+        else *(float4*)(Z + q * H) = make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+      return;
+    }
+  }
+  const bool slabs_on = !LIVE || len > p.step + 1;
   float g[4][4];
   const T* G = (const T*)p.gates + (size_t)m * 4 * H + u;
 #pragma unroll
@@ -108,7 +128,7 @@ __global__ __launch_bounds__(NT) void lstm_bwd_vec4_kernel(const UicLstmBwdParam
   float4 ds = make_float4(0.f, 0.f, 0.f, 0.f);       // split-K partial slabs of two more sources, summed in a fixed order
 #pragma unroll
   for (int z = 0; z < 8; ++z) {
-    const bool use = z < 4 ? z < nA : z - 4 < nB;
+    const bool use = (z < 4 ? z < nA : z - 4 < nB) && slabs_on;
     ds.x += use ? sv[z].x : 0.f; ds.y += use ? sv[z].y : 0.f; ds.z += use ? sv[z].z : 0.f; ds.w += use ? sv[z].w : 0.f;
   }
   const float4 cp = hascp ? cpr : make_float4(0.f, 0.f, 0.f, 0.f);
@@ -141,6 +161,13 @@ __global__ __launch_bounds__(NT) void lstm_bwd_vec4_kernel(const UicLstmBwdParam
   for (int q = 0; q < 4; ++q) {
     if constexpr (sizeof(T) == 2) *(uint2*)(D + q * H) = make_uint2(uic_pack_bf16x2(o[q][0], o[q][1]), uic_pack_bf16x2(o[q][2], o[q][3]));
     else *(float4*)(D + q * H) = make_float4(o[q][0], o[q][1], o[q][2], o[q][3]);
+  }
+  if constexpr (LIVE && sizeof(T) == 2) {
+    if (p.dgates_c) {                                  // the same row again, where the step's d x GEMM reads its A operand
+      T* Dc = (T*)p.dgates_c + (size_t)rk * 4 * H + u;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) *(uint2*)(Dc + q * H) = make_uint2(uic_pack_bf16x2(o[q][0], o[q][1]), uic_pack_bf16x2(o[q][2], o[q][3]));
+    }
   }
   *(float4*)(p.dc + idx) = make_float4(dcn[0], dcn[1], dcn[2], dcn[3]);
 }
@@ -189,6 +216,8 @@ static int lstm_bwd_check(const UicLstmBwdParams& p, const char* who) {
               (!p.nB || p.ldB >= p.H), "%s: a leading dimension below H=%d (lddh %d %d %d, ldA %d, ldB %d)", who, p.H, p.lddh0, p.lddh1,
               p.lddh2, p.ldA, p.ldB);
   UIC_REQUIRE(p.drop_p >= 0.f && p.drop_p < 1.f, "%s: drop_p=%f outside [0, 1)", who, (double)p.drop_p);
+  UIC_REQUIRE(p.row_len || (!p.rank && !p.dgates_c), "%s: rank / dgates_c without row_len", who);
+  UIC_REQUIRE(!p.row_len || (p.step >= 0 && (!p.dgates_c || p.rank)), "%s: row_len needs step=%d >= 0, dgates_c needs rank", who, p.step);
   return UIC_OK;
 }
 int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kernel_id) {
@@ -217,7 +246,11 @@ int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kerne
     const dim3 g4((unsigned)((h4 + bt - 1) / bt), (unsigned)p.M);
     const bool simple = p.dh0 && !p.dh1 && !p.dh2 && p.c_prev;
     if (kernel_id) *kernel_id = simple ? UIC_LSTM_BWD_VEC4_SIMPLE : UIC_LSTM_BWD_VEC4;
-    if (simple) {
+    UIC_REQUIRE(!p.row_len || (simple && p.dtype == UIC_BF16 && (!p.dgates_c || ((uintptr_t)p.dgates_c & 7) == 0)),
+                "lstm_bwd: row_len is taken by the bf16 four-units-per-lane kernel with dh0 and c_prev only");
+    if (p.row_len) {
+      hipLaunchKernelGGL((lstm_bwd_vec4_kernel<bf16_t, true, true>), g4, dim3(bt), 0, s, p);
+    } else if (simple) {
       UIC_DISPATCH_T(p.dtype, hipLaunchKernelGGL((lstm_bwd_vec4_kernel<bf16_t, true>), g4, dim3(bt), 0, s, p),
                      hipLaunchKernelGGL((lstm_bwd_vec4_kernel<float, true>), g4, dim3(bt), 0, s, p));
     } else {
@@ -227,6 +260,7 @@ int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kerne
     UIC_LAUNCH_CHECK("lstm_bwd_vec4");
     return UIC_OK;
   }
+  UIC_REQUIRE(!p.row_len, "lstm_bwd: row_len needs the four-units-per-lane kernel (M H >= 65536, H %% 4 == 0, aligned operands below 2^31 bytes)");
   const int g = uic_grid_for((size_t)p.M * p.H, NT);
   UIC_DISPATCH_T(p.dtype, hipLaunchKernelGGL(lstm_bwd_kernel<bf16_t>, dim3(g), dim3(NT), 0, s, p),
                  hipLaunchKernelGGL(lstm_bwd_kernel<float>, dim3(g), dim3(NT), 0, s, p));
@@ -235,7 +269,7 @@ int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kerne
 }
 int uic_maxout_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s) {
   UIC_TRY(lstm_bwd_check(p, "maxout_lstm_bwd"));
-  UIC_REQUIRE(!p.dh2 && !p.nA && !p.nB, "maxout_lstm_bwd: takes dh0 and dh1 only");
+  UIC_REQUIRE(!p.dh2 && !p.nA && !p.nB && !p.row_len, "maxout_lstm_bwd: takes dh0 and dh1 only");
   if (p.M == 0) return UIC_OK;
   const int g = uic_grid_for((size_t)p.M * p.H, NT);
   UIC_DISPATCH_T(p.dtype, hipLaunchKernelGGL(maxout_lstm_bwd_kernel<bf16_t>, dim3(g), dim3(NT), 0, s, p),

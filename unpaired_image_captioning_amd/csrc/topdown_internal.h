@@ -29,6 +29,10 @@ struct Layout {
   int* cap_len;                                 // ... [N]: 1 + the last decode step at which the row has a live position (the BPTT steps behind it are zeros)
   int* live_inv;                                // ... and its inverse [T N]: position -> list index or -1 (the recurrence stores hdrop rows by it)
   int* live_map;                                // the live list made on the device (uic_topdown_batch.live_rows == NULL): [T N + 128]
+  // the rows by caption length, longest first (uic_live_list_launch's UicLiveOrder): [N], its inverse [N], and per decode step the
+  // number of rows whose caption has not ended [T + 1]; dG2 / dG1 of ONE decode step with the unfinished rows in that order
+  // [N, 4H] -- the compact A operands of the BPTT loop's two d x GEMMs (Step::bwd_step)
+  int* row_order; int* row_rank; int* unfinished; void* dg2c; void* dg1c;
   void* hc; float* dhc;                         // live-position logit layer (uic_topdown_batch.live_rows): the live rows of hdrop, operand dtype
                                                 // [T N + 128, H]; their d hdrop, f32 [T N, H]
   void* lh[UIC_MAX_LOGIT_LAYERS - 1];       // logit_layers > 1: dropout(relu(hidden logit block l)) [T*N, H]
@@ -132,6 +136,7 @@ struct SideStream {
   hipEvent_t ev_main[MAX_CHUNKS];   // main  -> side: decode steps of chunk c are finished
   hipEvent_t ev_side[MAX_CHUNKS];   // side  -> main: d hdrop of chunk c is ready
   bool ready = false;
+  int compact_launches = 0;         // uic_topdown_compact_launches: of the last fused step
   // uic_topdown_step_marks: timing events of the last fused step (only recorded while marks_on)
   bool marks_on = false, marks_valid = false;
   hipEvent_t mark[UIC_STEP_MARKS];
@@ -185,6 +190,16 @@ struct Step {
   // computes every position with per-position weights (the self-critical step: a sampled caption's positions behind its end weigh
   // zero) -- by the list kernel alone.
   bool have_len = false;
+  // rows_by_len (uic_topdown_batch.unfinished_count, with have_len on the split-K chain): the two d x GEMMs of a BPTT step whose
+  // unfinished rows fill fewer 128-row tiles than the batch run over those rows only (compact_step), A from L.dg2c / L.dg1c --
+  // the cell backward kernels store the unfinished rows there a second time, by rank -- and the slab rows placed by L.row_order,
+  // so the slabs stay position-indexed; their consumers take zeros for the rows that were not written.  Every gradient of an
+  // ended row is an exact zero and an output row of the GEMM depends on its own A row only: the results do not change.
+  bool rows_by_len = false;
+  int unf[UIC_MAX_LIVE_STEPS + 1];
+  int compact_launches = 0;      // d x GEMM launches of this step that took the compact form
+  void init_rows_by_len();
+  bool compact_step(int t) const { return rows_by_len && unf[t] > 0 && (unf[t] + 127) / 128 < (N + 127) / 128; }
   int len_build(hipStream_t s);
   int live_build(hipStream_t s);
   int embed_split = 0;           // > 0: ... into the halves [0, embed_split) / [embed_split, t_run) of the decode steps (embed_grad)

@@ -163,6 +163,11 @@ Layout make_layout(const uic_topdown_dims& d, void* ws) {
   L.bm_done_p = (float*)b.take(N * T * 4);
   L.bm_done_seq = (int64_t*)b.take(N * T * T * 8);
   L.bm_done_lp = (float*)b.take(N * T * T * 4);
+  L.row_order = (int*)b.take(N * 4);
+  L.row_rank = (int*)b.take(N * 4);
+  L.unfinished = (int*)b.take((T + 1) * 4);
+  L.dg2c = b.take(N * 4 * H * S);
+  L.dg1c = b.take(N * 4 * H * S);
   L.total = (b.off + 255) & ~(size_t)255;
   return L;
 }
@@ -254,7 +259,8 @@ void* uic_topdown_workspace_ptr(const uic_topdown_dims* d, void* workspace, cons
       {"datth", L.datth_all}, {"d_att", L.d_att}, {"d_p_att", L.d_patt}, {"dxt", L.dxt}, {"rnn_dbg", L.rnn_dbg}, {"rnn_bwd_dbg", L.rnn_bwd_dbg},
       // ("dx1", and columns [H, 3H) of "dx2": written only when the d x GEMMs are not split-K, i.e. by the persistent BPTT kernel
       // or at shapes where bptt_split() == 0 -- the split chain keeps these sums in its slabs)
-      {"dx1", L.dx1}, {"dc_att", L.dc_att}, {"dc_lang", L.dc_lang}};
+      {"dx1", L.dx1}, {"dc_att", L.dc_att}, {"dc_lang", L.dc_lang},
+      {"cap_len", L.cap_len}, {"row_order", L.row_order}, {"row_rank", L.row_rank}, {"unfinished", L.unfinished}};
   for (auto& e : tab)
     if (!strcmp(e.n, name)) return e.p;
   return nullptr;

@@ -38,14 +38,30 @@ void Step::init_live() {
   live_rows = build_live ? L.live_map : b->live_rows;
   compact = true;
 }
+// after init_live, before live_build.  The counts size launches and nothing else: whatever they hold, every launch stays inside its
+// buffers (0 <= count <= N rows of an [N, 4H] operand; the map's entries are the device's own, each below N) -- counts that are not
+// those of the masks are reported by the list kernel through the status word, never by a fault.
+void Step::init_rows_by_len() {
+  rows_by_len = false;
+  compact_launches = 0;
+  if (!b->unfinished_count || !compact || !build_live || !d.rnn_status || dt != UIC_BF16 || !bptt_split() || !uic_live_order_ok(N, t_run)) return;
+  if ((size_t)N * H < 65536 || H % 32 != 0 || A % 128 != 0 || A > 512 || A == 384) return;   // (the two cell backward kernels that take row_len)
+  for (int t = 0; t < t_run; ++t) {
+    unf[t] = b->unfinished_count[t];
+    if (unf[t] < 0 || unf[t] > N) return;
+  }
+  unf[t_run] = 0;
+  rows_by_len = true;
+}
 int Step::len_build(hipStream_t s) {
   return uic_live_list_launch(b->grad_scale, b->ld_grad_scale, 0, N, t_run * N, L.live_map, 0, s, nullptr, nullptr, 0, L.cap_len);
 }
 int Step::live_build(hipStream_t s) {
   const size_t S = uic_dtype_size(dt);
+  const UicLiveOrder ord{L.row_order, L.row_rank, L.unfinished, b->unfinished_count, d.rnn_status};
   return uic_live_list_launch(b->masks, b->ld_masks, 1, N, t_run * N, L.live_map, live_pad(), s, fused_gather ? L.live_inv : nullptr,
                               fused_gather ? offw(L.hc, (size_t)live_total() * H, dt) : nullptr,
-                              fused_gather ? (size_t)(live_pad() - live_total()) * H * S : 0, L.cap_len);
+                              fused_gather ? (size_t)(live_pad() - live_total()) * H * S : 0, L.cap_len, rows_by_len ? &ord : nullptr);
 }
 
 // ---------------------------------------------------------------- forward
@@ -414,6 +430,7 @@ int Step::bwd_step(int t, hipStream_t s) {
   float* slab2 = L.bp_slab2[t & 1];
   const float* slab2_next = L.bp_slab2[(t + 1) & 1];
   const size_t st2 = (size_t)N * 3 * H, st1 = (size_t)N * 2 * H;
+  const bool cm = compact_step(t);       // this step's d x GEMMs run over the unfinished rows only
   {
     UicLstmBwdParams p;
     memset(&p, 0, sizeof(p));
@@ -427,11 +444,13 @@ int Step::bwd_step(int t, hipStream_t s) {
     p.dc = L.dc_lang; p.gates = off(L.gates2, (size_t)t * N * H4, dt);
     p.c_prev = L.c_lang + t * NH; p.c = L.c_lang + (t + 1) * NH;
     p.dgates = offw(L.dg2_all, (size_t)t * N * H4, dt);
+    if (rows_by_len) { p.row_len = L.cap_len; p.rank = L.row_rank; p.step = t; p.dgates_c = cm ? L.dg2c : nullptr; }
     UIC_TRY(uic_lstm_bwd_launch(p, s));
   }
   {  // d[att_res | h_att | h_lang_prev] = dG2 [W_ih | W_hh]
-    UicGemmParams g = gemm_base(dt, N, 3 * H);
-    add_seg(g, off(L.dg2_all, (size_t)t * N * H4, dt), H4, dv.w2T, H4, H4);
+    UicGemmParams g = gemm_base(dt, cm ? unf[t] : N, 3 * H);
+    add_seg(g, cm ? L.dg2c : off(L.dg2_all, (size_t)t * N * H4, dt), H4, dv.w2T, H4, H4);
+    if (cm) { g.slab_row_map = L.row_order; g.slab_rows = N; ++compact_launches; }
     if (S) { g.slab = slab2; g.splitk = S; }
     else { g.C = dx2; g.ldc = 3 * H; g.flags = UIC_GEMM_OUT_F32; }
     UIC_TRY(uic_gemm_launch(g, s));
@@ -459,8 +478,10 @@ int Step::bwd_step(int t, hipStream_t s) {
     hc.dc = L.dc_att; hc.gates = off(L.gates1, (size_t)t * N * H4, dt);
     hc.c_prev = L.c_att + t * NH; hc.c = L.c_att + (t + 1) * NH;
     hc.dgates = offw(L.dg1_all, (size_t)t * N * H4, dt);
+    if (rows_by_len) { hc.row_len = L.cap_len; hc.rank = L.row_rank; hc.step = t; hc.dgates_c = cm && t > 0 ? L.dg1c : nullptr; }
   }
   const bool fused_cell = S && uic_h2att_cell_bwd_eligible(hc);
+  UIC_REQUIRE(fused_cell || !rows_by_len, "bwd_step: rows by length need the fused h2att + cell backward kernel");
   if (fused_cell) {
     UIC_TRY(uic_h2att_cell_bwd_launch(hc, s));
   } else {
@@ -486,8 +507,9 @@ int Step::bwd_step(int t, hipStream_t s) {
   }
   }
   if (t > 0) {  // d[h_lang_prev | h_att_prev] = dG1 [W_ih[:, :H] | W_hh]
-    UicGemmParams g = gemm_base(dt, N, 2 * H);
-    add_seg(g, off(L.dg1_all, (size_t)t * N * H4, dt), H4, dv.w1recT, H4, H4);
+    UicGemmParams g = gemm_base(dt, cm ? unf[t] : N, 2 * H);
+    add_seg(g, cm ? L.dg1c : off(L.dg1_all, (size_t)t * N * H4, dt), H4, dv.w1recT, H4, H4);
+    if (cm) { g.slab_row_map = L.row_order; g.slab_rows = N; ++compact_launches; }
     if (S) { g.slab = L.bp_slab1; g.splitk = S; }
     else { g.C = L.dx1; g.ldc = 2 * H; g.flags = UIC_GEMM_OUT_F32; }
     UIC_TRY(uic_gemm_launch(g, s));

@@ -105,6 +105,7 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   // the single-stream uic_topdown_backward call only, where nothing runs beside it.
   st.d.recurrence &= ~UIC_REC_BWD_PERSIST;
   st.init_live();
+  st.init_rows_by_len();
   const bool early = st.early_grads();
   ss->embed_recorded = false;
   // UIC_REC_COMM_STREAM: a communication stream of the caller is busy beside this step (data parallel).  The chip dispatches
@@ -321,6 +322,7 @@ int uic_topdown_xe_train_step(const uic_topdown_dims* d, const uic_topdown_weigh
   UIC_MARK(8, s2);
   UIC_HIP(hipStreamWaitEvent(s, ss->ev_early, 0));    // join
   UIC_MARK(9, s);
+  ss->compact_launches = st.compact_launches;
   ss->marks_valid = ss->marks_on;
 #undef UIC_MARK
 #undef UIC_HIP
@@ -339,6 +341,14 @@ int uic_topdown_step_marks(int32_t enable, float* ms_out) {
   }
   ss->marks_on = enable != 0;
   if (!ss->marks_on) ss->marks_valid = false;
+  return UIC_OK;
+}
+
+int uic_topdown_compact_launches(int32_t* out) {
+  SideStream* ss = nullptr;
+  UIC_TRY(get_side(&ss));
+  UIC_REQUIRE(out, "compact_launches: null pointer");
+  *out = ss->compact_launches;
   return UIC_OK;
 }
 

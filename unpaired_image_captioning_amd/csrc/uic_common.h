@@ -252,6 +252,10 @@ struct UicGemmParams {
   // ---- split-K over workgroups (large-GEMM path only): slice z of `splitk` writes its raw partial tile to
   // slab[z][M][N] (f32, dense); uic_splitk_reduce_launch sums the slabs in a fixed order (deterministic)
   int splitk; float* slab;
+  // optional, with slab: output row i < M of the product goes to row slab_row_map[i] of a slab of slab_rows rows (slice stride
+  // slab_rows * N); an entry outside [0, slab_rows) drops its row.  The A operand is then a compact list of the rows that have a
+  // result at all -- the BPTT loop's d x GEMMs over the unfinished captions -- while the slab keeps its consumers' row order.
+  const int* slab_row_map; int slab_rows;
   // ---- fused backward-of-ReLU epilogue (ping-pong kernel only, gemm_pp.hip): v = (acc + acc_src[row, col]); then, with
   // mask_act (operand dtype, the forward activation), v = mask_act[row, col] > 0 ? v * mask_scale : 0 -- d att' = d p_att W_ctx2att
   // + the attention's own share, masked by att' > 0 and scaled by the dropout keep factor, written as the bf16 operand of
@@ -663,6 +667,11 @@ struct UicLstmBwdParams {
   const float* c_prev;           // [M,H] or null
   const float* c;                // [M,H]
   void* dgates;                  // [M,4H] operand dtype out
+  // optional (the four-units-per-lane SIMPLE kernel, bf16): the caption lengths of the rows and the decode step of this call.  A row
+  // with row_len <= step writes a zero dgates row and leaves (d c untouched); one with row_len == step + 1 takes exact zeros for both
+  // slab sources (their GEMMs ran over the unfinished rows only: its slab rows were never written); a row with row_len > step also
+  // stores its dgates row at row rank[m] of dgates_c (optional: the compact A operand of the step's d x GEMM)
+  const int* row_len; const int* rank; int step; void* dgates_c;
 };
 // kernel_id (host, optional): which kernel ran (UIC_LSTM_BWD_SCALAR / _VEC4 / _VEC4_SIMPLE, include/uic_hip.h)
 int uic_lstm_bwd_launch(const UicLstmBwdParams& p, hipStream_t s, int32_t* kernel_id = nullptr);
@@ -681,6 +690,10 @@ struct UicH2attCellParams {
   const float* c_prev;           // [N, H] or null
   const float* c;                // [N, H]
   void* dgates;                  // [N, 4H] out
+  // optional: caption lengths and the decode step (see UicLstmBwdParams).  slabA is THIS step's d x2 GEMM -- zeros for a row with
+  // row_len <= step --, slabB the next step's d x1 -- zeros for row_len <= step + 1; rows with row_len > step are stored at row
+  // rank[n] of dgates_c as well (optional)
+  const int* row_len; const int* rank; int step; void* dgates_c;
 };
 bool uic_h2att_cell_bwd_eligible(const UicH2attCellParams& p);
 int uic_h2att_cell_bwd_launch(const UicH2attCellParams& p, hipStream_t s);
@@ -722,8 +735,14 @@ int uic_reward_crit_launch(int N, int L, const float* logp, const int64_t* seq, 
 // the ascending list of the positions t * N + n (p < M) with mask[n * ld + col0 + t] != 0, padded with -1 up to out_len entries
 // inv (optional, [M]): inv[p] = the list index of position p or -1; zero / zero_bytes (optional): a region cleared by the same launch
 // row_len (optional, [N]): row_len[n] = 1 + the last t with mask[n, col0 + t] != 0 (0: none)
+// order (optional, with row_len): the rows sorted by row_len, longest first, rows of equal length in ascending order -- the rows with
+// row_len > t are order[0 .. unfinished[t]) for EVERY t, so one permutation serves all decode steps; rank = its inverse;
+// unfinished [T + 1].  expect (optional, host [T]): the counts the caller sized its launches with -- where unfinished[t] differs
+// the kernel sets status[0] = UIC_STATUS_UNFINISHED_COUNT | t (the first such t), and the caller's next look at the status fails
+struct UicLiveOrder { int* order; int* rank; int* unfinished; const int* expect; unsigned* status; };
+bool uic_live_order_ok(int N, int T);
 int uic_live_list_launch(const float* mask, int ld, int col0, int N, int M, int* out, int out_len, hipStream_t s, int* inv = nullptr,
-                         void* zero = nullptr, size_t zero_bytes = 0, int* row_len = nullptr);
+                         void* zero = nullptr, size_t zero_bytes = 0, int* row_len = nullptr, const UicLiveOrder* order = nullptr);
 // rows by index: out[m] = src[map[m]] (rows [M, Mpad) of out, and rows whose index is outside [0, src_rows), cleared) /
 // dst[map[m]] = src[m] (indices outside [0, dst_rows) skipped); row_bytes % 16 == 0
 int uic_gather_rows_launch(const void* src, const int* map, int src_rows, void* out, int M, int Mpad, size_t row_bytes, hipStream_t s);

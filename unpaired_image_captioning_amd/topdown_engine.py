@@ -218,10 +218,12 @@ class TopDownEngine(object):
     def batch_struct(self, fc, att, att_masks, labels=None, masks=None, grad_scale=None, ss_prob=0.0, d_fc=None, d_att=None, live=None):
         """live: (live_rows, live_count) -- uic_topdown_batch.live_rows / live_count: the per-step counts of unmasked positions (host
         int32 numpy, live_counts(masks)) and, optionally, the list itself (device int32, live_positions(masks)); with live_rows
-        None the step compacts the masks on the device."""
+        None the step compacts the masks on the device.  A third entry (optional): uic_topdown_batch.unfinished_count, host int32
+        numpy, unfinished_counts(masks)."""
         b = Batch()
         if live is not None and live[1] is not None:
-            rows, count = live
+            rows, count = live[0], live[1]
+            unfinished = live[2] if len(live) > 2 else None
             count = np.ascontiguousarray(count, dtype=np.int32)
             T = (labels.shape[1] - 1) if labels is not None else 0
             if count.shape != (T,):
@@ -234,6 +236,12 @@ class TopDownEngine(object):
                 b.live_rows = rows.data_ptr()
             b._keep_live = (rows, count)
             b.live_count = count.ctypes.data_as(C.POINTER(C.c_int32))
+            if unfinished is not None:
+                unfinished = np.ascontiguousarray(unfinished, dtype=np.int32)
+                if unfinished.shape != (T,):
+                    raise ValueError("unfinished_count must hold one entry per decode step (%d)" % T)
+                b._keep_live = (rows, count, unfinished)
+                b.unfinished_count = unfinished.ctypes.data_as(C.POINTER(C.c_int32))
         att = self._pad_att(att)
         b._keep = att                          # (a padded copy must outlive the call)
         b.d_fc_feats = ptr(d_fc)
@@ -530,6 +538,17 @@ def live_counts(masks):
     array (the loader makes it on the host, P/misc/dataloader/dataloader.py:200-203) -> int32 numpy [T]."""
     m = masks.detach().cpu().numpy() if torch.is_tensor(masks) else np.asarray(masks)
     return np.count_nonzero(m[:, 1:], axis=0).astype(np.int32)
+
+
+def unfinished_counts(masks):
+    """Per decode step t, the number of rows whose caption has not ended (uic_topdown_batch.unfinished_count): a row's caption ends
+    behind its last non-zero mask, so a hole in a row's masks does not end it -- there this differs from live_counts.
+    masks [N, T + 1] host array or tensor -> int32 numpy [T]."""
+    m = masks.detach().cpu().numpy() if torch.is_tensor(masks) else np.asarray(masks)
+    on = m[:, 1:] != 0
+    T = on.shape[1]
+    length = np.where(on.any(axis=1), T - np.argmax(on[:, ::-1], axis=1), 0)      # 1 + the last non-zero position, 0: none
+    return (length[:, None] > np.arange(T)[None, :]).sum(axis=0).astype(np.int32)
 
 
 def live_positions(masks, device=None):

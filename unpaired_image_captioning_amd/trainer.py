@@ -15,7 +15,7 @@ import torch
 
 from . import _lib, models
 from ._lib import check
-from .topdown_engine import live_counts
+from .topdown_engine import live_counts, unfinished_counts
 from .misc.optimizer import FlatArena, Optim  # noqa: F401
 from .parallel_exchange import GradientExchange
 
@@ -47,7 +47,7 @@ def xe_step(model, batch, t_run=None, inv_den=None, grads=None, return_seed=Fals
     if fused:
         if grads is None:
             grads = {k: torch.empty_like(v) for k, v in pd.items()}
-        live = (batch.get("live_rows"), batch["live_count"]) if batch.get("live_count") is not None else None
+        live = (batch.get("live_rows"), batch["live_count"], batch.get("unfinished_count")) if batch.get("live_count") is not None else None
         out = eng.xe_train_step(pd, batch["fc_feats"], batch["att_feats"], batch.get("att_masks"), labels, batch["masks"],
                                 t_run, training, seed, grads, inv_den, ss_prob=ss_prob, d_fc=d_fc, d_att=d_att, out=out, live=live)
         if return_seed:
@@ -287,6 +287,7 @@ class Trainer(object):
             # loader made the masks: the step's logit layer and criterion skip the others (uic_topdown_batch.live_count: the step
             # compacts the device masks itself, nothing more is shipped; opt.live_positions = 0 computes every position)
             out["live_count"] = live_counts(data["masks"])
+            out["unfinished_count"] = unfinished_counts(data["masks"])
         return out
 
     @staticmethod
@@ -294,6 +295,7 @@ class Trainer(object):
         """Adds the per-step counts of unmasked positions to a DEVICE batch (a resident benchmark batch; Trainer.to_device does it
         for host batches).  One device-to-host read of the masks: call it once per batch, outside a timed region."""
         batch["live_count"] = live_counts(batch["masks"])
+        batch["unfinished_count"] = unfinished_counts(batch["masks"])     # (rows per step the BPTT loop's d x GEMMs run over)
         return batch
 
     def _ship(self, key, t, dtype):
