@@ -479,6 +479,38 @@ def test_nmt_translate_bf16_mid_size_vs_oracle():
     assert n_same >= cfg["B"] // 2, n_same
 
 
+@pytest.mark.parametrize("S", [5, 33])
+def test_nmt_translate_fast_attention_vs_oracle(S):
+    """The translator's attention call at bf16, rnn_size 512 -- query from linear_in, source padding masked, no hoisted
+    context x W_in -- goes to the register-resident kernels (8 source positions per wave at S = 5, 16 at S = 33), a mode the
+    training step never uses.  Bounds of the bf16 mid-size test; besides, the winning hypotheses' attention (PAD columns
+    dropped, packed left) is exactly zero behind the valid positions and -- what only the mask can give -- sums to 1 over
+    them: an unmasked PAD position would keep its share.  (The oracle alone, f32 against bf16-rounded weights,
+    for these seeds: scores within 0.032 of a bound of 1.69 at S = 5, 0.027 of 0.72 at S = 33, all three hypotheses
+    identical; 8 and 3 decoder steps.)"""
+    cfg = dict(layers=2, H=512, W=512, B=3, S=S, T=2, Vs=60, Vt=40)
+    W = random_weights(cfg, 31, scale=0.2)
+    W["generator.0.bias"][3] += 3.0
+    I = synthetic(dict(cfg, T=6), 9)
+    valid = [int(n) for n in I["lengths"].view(-1)]
+    assert min(valid) < S
+    model, _ = build(cfg, W, "bf16")
+    model.eval()
+    batch = argparse.Namespace(src=I["src"].cuda(), batchSize=cfg["B"])
+    allHyp, allScores, allAttn, gold = model.translateBatch(batch, max_steps=8)
+    hyp_o, scores_o, attn_o = ON.translate_batch(W, I["src"], max_steps=8)
+    n_same = sum(int(allHyp[b][0] == [int(t) for t in hyp_o[b]]) for b in range(cfg["B"])) if len(allHyp[0][0]) == hyp_o.shape[1] else 0
+    got = torch.stack([s_[0] for s_ in allScores]).cpu()
+    print("scores", got.tolist(), "oracle", scores_o.tolist(), "n_same", n_same, "steps", len(allHyp[0][0]), hyp_o.shape[1])
+    assert (got - scores_o).abs().max().item() < 0.15 * max(1.0, scores_o.abs().max().item()), (got, scores_o)
+    assert n_same >= cfg["B"] // 2, n_same
+    for b in range(cfg["B"]):
+        a = allAttn[b][0]                                              # [steps, valid positions], a view of [B, max_steps, S]
+        assert a.shape[1] == valid[b] and a.shape[0] == len(allHyp[b][0])
+        assert a._base[b, :a.shape[0], valid[b]:].abs().max().item() == 0 if valid[b] < S else True
+        assert (a.sum(1) - 1).abs().max().item() < 1e-3, (b, a.sum(1))
+
+
 @pytest.mark.parametrize("cfg", _nmt_sweep(10, 4242), ids=lambda c: "tr%d" % c["idx"])
 def test_nmt_translate_random_sweep_vs_oracle(cfg):
     """10 seeded random configurations through translateBatch (beam 15, f32): the oracle's hypotheses token for token for

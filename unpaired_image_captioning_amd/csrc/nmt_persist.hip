@@ -21,11 +21,9 @@
 // nmt_dec_persist_kernel (batch <= 640, any layer count): the generic form, weights re-read every step, 8 groups of <= 80 rows.
 // bf16 operands, rnn_size 512, source length <= 64; anything else keeps the per-step launches.
 #include "rnn_persist_common.h"
+#include "nmt_internal.h"   // the dropout site numbers
 
 namespace {
-
-#define NMT_SITE_DEC(l, t) (2000u + (unsigned)(l) * 256u + (unsigned)(t))     // (as csrc/nmt.hip)
-#define NMT_SITE_OUT(t) (4000u + (unsigned)(t))
 
 constexpr int NMT_MAXR = 8;           // source positions per wave: S <= NWAVE * NMT_MAXR = 64
 
@@ -67,7 +65,7 @@ __device__ __forceinline__ void linout_phase(Ctx& c, const T* cvec, const T* q, 
 
 // dot attention of the rows this workgroup takes in the attention phase: scores = ctxw[s, b, :] . q, softmax over the source
 // positions (no padding mask in the training forward, as in the reference), c = sum_s a[s] ctx[s, b, :].  Every global load of
-// a row is issued at its top (csrc/nmt.hip's gattn_fwd_fast_kernel, here with 8 waves and the query read past the L1).
+// a row is issued at its top (csrc/nmt_kernels.hip's gattn_fwd_fast_kernel, here with 8 waves and the query read past the L1).
 template <bool SAFE>
 __device__ __forceinline__ void nmt_attn_phase(const Ctx& c, const UicNmtDecParams& p, const bf16_t* q_all, float* attn_t, bf16_t* cvec_t) {
   const int S = p.S, B = p.B;
@@ -173,7 +171,7 @@ __device__ __forceinline__ void nmt_dec_steps(const UicNmtDecParams& p, Ctx& c) 
         const int ldb[2] = {p.ld_ih[0], HH};
         const float* gx = p.gx_d0 + (size_t)t * B * 4 * HH;
         auto pre = [&](unsigned idx4, unsigned) { return gx[idx4]; };
-        lstm_phase<T, SAFE, 2>(c, As, Bs, ldb, pre, cprev, cnew, h_new, hdrop, gates, B, inter ? p.drop_p : 0.f, p.seed, NMT_SITE_DEC(0, t));
+        lstm_phase<T, SAFE, 2>(c, As, Bs, ldb, pre, cprev, cnew, h_new, hdrop, gates, B, inter ? p.drop_p : 0.f, p.seed, SITE_NMT_DEC(0, t));
       } else {
         const void* const As[2] = {x + rb, h_prev + rb};
         const void* const Bs[2] = {p.w_ih[l], p.w_hh[l]};
@@ -181,7 +179,7 @@ __device__ __forceinline__ void nmt_dec_steps(const UicNmtDecParams& p, Ctx& c) 
         const float* b1 = p.b_ih[l];
         const float* b2 = p.b_hh[l];
         auto pre = [&](unsigned, unsigned col) { return b1[col] + b2[col]; };
-        lstm_phase<T, SAFE, 2>(c, As, Bs, ldb, pre, cprev, cnew, h_new, hdrop, gates, B, inter ? p.drop_p : 0.f, p.seed, NMT_SITE_DEC(l, t));
+        lstm_phase<T, SAFE, 2>(c, As, Bs, ldb, pre, cprev, cnew, h_new, hdrop, gates, B, inter ? p.drop_p : 0.f, p.seed, SITE_NMT_DEC(l, t));
       }
       x = inter ? hdrop : h_new;
       if (!group_barrier(c)) return;
@@ -191,7 +189,7 @@ __device__ __forceinline__ void nmt_dec_steps(const UicNmtDecParams& p, Ctx& c) 
     nmt_attn_phase<SAFE>(c, p, q, p.attn_all + (size_t)t * B * p.S, cvec);
     if (!group_barrier(c)) return;
     linout_phase<T, SAFE>(c, cvec + rb, q + rb, (const T*)p.attn_out_w, (T*)p.out_pre + (size_t)t * BH, (T*)p.out_all + (size_t)(t + 1) * BH,
-                          p.drop_p, p.seed, NMT_SITE_OUT(t));
+                          p.drop_p, p.seed, SITE_NMT_OUT(t));
     if (!group_barrier(c)) return;
   }
 }
@@ -324,7 +322,7 @@ __device__ __forceinline__ void nmt_dec_ws_steps(const UicNmtDecParams& p, Ctx& 
       wr[uu][1] = *(const float4*)(p.ctxw + r + (c.lane + 64) * 4);
     }
   };
-  // dot attention of that row (GlobalAttention.py:120-160; csrc/nmt.hip gattn_fwd_fast_kernel): every wave reads the query in the
+  // dot attention of that row (GlobalAttention.py:120-160; csrc/nmt_kernels.hip gattn_fwd_fast_kernel): every wave reads the query in the
   // layout of its own products, takes source positions wave + 8 u, and redoes the <= 64-way softmax in its lanes (no LDS loops)
   auto attention = [&](const T* q_all, float* attn_t, T* cvec_t) {
     const int S = p.S;
@@ -394,7 +392,7 @@ __device__ __forceinline__ void nmt_dec_ws_steps(const UicNmtDecParams& p, Ctx& 
       lstm((const T*)p.out_all + (size_t)t * BH + rb, h0_prev + rb,
            [&](int j, int g) { return w0[((c.wave * 4 + j) * 4 + g) * 64 + c.lane]; }, pv, cs0,
            p.cd[0] + (size_t)(t + 1) * BH, h0_new, hdrop0, (T*)p.gates_d[0] + (size_t)t * B * 4 * HH,
-           two ? p.drop_p : 0.f, NMT_SITE_DEC(0, t));
+           two ? p.drop_p : 0.f, SITE_NMT_DEC(0, t));
     }
     FW_STAMP(1);
     group_arrive(c);
@@ -449,7 +447,7 @@ __device__ __forceinline__ void nmt_dec_ws_steps(const UicNmtDecParams& p, Ctx& 
           const unsigned o = nnw + u;
           const float v = uic_tanh<T>(sres);
           ((T*)p.out_pre)[(size_t)t * BH + o] = uic_from_f<T>(v);
-          st_x<SAFE>((T*)p.out_all + (size_t)(t + 1) * BH + o, p.drop_p > 0.f ? v * uic_drop_scale(p.seed, NMT_SITE_OUT(t), o, p.drop_p, inv_keep) : v);
+          st_x<SAFE>((T*)p.out_all + (size_t)(t + 1) * BH + o, p.drop_p > 0.f ? v * uic_drop_scale(p.seed, SITE_NMT_OUT(t), o, p.drop_p, inv_keep) : v);
         }
       }
       __syncthreads();
@@ -487,7 +485,7 @@ __global__ __launch_bounds__(NTH) void nmt_dec_persist_kernel(const UicNmtDecPar
 //   C  top layer: cell backward of the own 16 units (exchanged: d gates), then d [x_1 ; h_1(t-1)] = d gates W_1 -- own columns of
 //      both halves stay in registers (d x_1 = the gradient of layer 0's dropped h, d h_1(t-1) = the next step's carry)
 //   D  layer 0: cell backward, d gates exchanged, d [feed ; h_0(t-1)] = d gates W_0: d feed exchanged (everybody's next step A)
-// -- tanh_drop_bwd, the d[c;q] GEMM, gattn_bwd_step, 2 x (lstm_bwd + GEMM) of csrc/nmt.hip's chain: 7 launches per step.
+// -- tanh_drop_bwd, the d[c;q] GEMM, gattn_bwd_step, 2 x (lstm_bwd + GEMM) of csrc/nmt_train.hip's chain: 7 launches per step.
 // Five group barriers per step.  Resident: W_0^T's 32 rows x K 2048 (this workgroup's columns of both halves) as an LDS image
 // (128 KB), W_1^T's (128 KB) and W_out^T's (32 KB) in registers.  Exchange slabs are indexed by step (never rewritten inside a
 // launch: a reader's L2 cannot hold a stale line of them).
@@ -658,7 +656,7 @@ __device__ __forceinline__ void nmt_dec_bwd_steps(const UicNmtDecBwdParams& p, C
         uic_unpack<T>(aop[j], op);
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
-          if (p.drop_p > 0.f) g[k] *= uic_drop_scale(p.seed, NMT_SITE_OUT(t), e + (unsigned)k, p.drop_p, inv_keep);
+          if (p.drop_p > 0.f) g[k] *= uic_drop_scale(p.seed, SITE_NMT_OUT(t), e + (unsigned)k, p.drop_p, inv_keep);
           g[k] *= 1.f - op[k] * op[k];
         }
         const uint4 pk = uic_pack<T>(g);
@@ -685,7 +683,7 @@ __device__ __forceinline__ void nmt_dec_bwd_steps(const UicNmtDecBwdParams& p, C
     }
     if (!group_wait(c, (int*)c.smem)) return;
     BW_STAMP(2);
-    if (att_wg) {  // ---- phase B: attention backward of row `rank` of the group (csrc/nmt.hip gattn_bwd_step_fast_kernel)
+    if (att_wg) {  // ---- phase B: attention backward of row `rank` of the group (csrc/nmt_kernels.hip gattn_bwd_step_fast_kernel)
       const int b = c.rbegin + c.rank;
       float* s_da = (float*)c.smem + 64;       // [64]
       float* s_red = s_da + 64;                // [BW_NW][HH]
@@ -759,7 +757,7 @@ __device__ __forceinline__ void nmt_dec_bwd_steps(const UicNmtDecBwdParams& p, C
     }
     {  // ---- phase D1: layer 0's cell backward (its h went through the inter-layer dropout)
       float v = dx1;
-      if (p.drop_p > 0.f) v *= uic_drop_scale(p.seed, NMT_SITE_DEC(0, t), nnw + u, p.drop_p, inv_keep);
+      if (p.drop_p > 0.f) v *= uic_drop_scale(p.seed, SITE_NMT_DEC(0, t), nnw + u, p.drop_p, inv_keep);
       cell_bwd(0, t, q0, v + dh0_rec, dc0);
     }
     BW_STAMP(7);

@@ -1,4 +1,4 @@
-// Host-side helpers shared by the launchers and the model-level sequencers (topdown_*.hip, fcmodel.hip, nmt.hip).
+// Host-side helpers shared by the launchers and the model-level sequencers (topdown_*.hip, fcmodel.hip, nmt_*.hip).
 #pragma once
 #include "uic_common.h"
 #include <string.h>

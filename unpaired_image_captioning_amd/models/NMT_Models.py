@@ -1,6 +1,6 @@
 """The pivot NMT teacher (zh -> en) behind the reference's constructors, state_dict keys and call contract
 (P/models/NMT_Models.py:27-135 Embeddings/Encoder, :137-271 Decoder, :272-420 NMTModel), computed by libuic_hip.so
-(`uic_nmt_forward_loss` / `uic_nmt_backward`, csrc/nmt.hip).
+(`uic_nmt_forward_loss` / `uic_nmt_backward`, csrc/nmt_train.hip; the translator: csrc/nmt_translate.hip).
 
 The reference runs the model and the loss as two python calls (P/trainer.py:178-179):
 
