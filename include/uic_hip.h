@@ -449,6 +449,37 @@ int uic_fc_sample(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdo
  * holds every image replicated beam_size times (N = images * beam_size).  seq / seq_logp: [images, L]. */
 int uic_fc_sample_beam(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* b, int32_t L, int32_t beam_size,
                        int32_t decoding_constraint, int32_t max_ppl, void* workspace, int64_t* seq, float* seq_logp, void* stream);
+/* The XE step of Trainer.train on the `fc` model (P/trainer.py:164-165,169-170: forward, LanguageModelCriterion, backward) in
+ * one call on one stream: uic_fc_forward(logprobs_out = NULL), uic_fc_xe_loss, uic_fc_backward(dlogprobs = NULL) on the same
+ * workspace -- the same launches in the same order, so every result is bit for bit that of the three calls.
+ * batch: fc_feats [N, Dfc], labels [N, >= S] int64, masks [N, >= S]; inv_den: optional device scalar 1 / (mask sum of the whole
+ * batch), as uic_fc_xe_loss; loss_out: 2 device floats, [loss, sum(mask) of this batch]; grads: DESTINATION pointers, every
+ * tensor is overwritten (no accumulation, no floating-point atomics: two calls with one seed give identical bits).
+ * Refused (non-zero, uic_last_error_string(), nothing launched): a null pointer, s_run outside [2, S], fewer than S label / mask
+ * columns, Dfc / H / E not multiples of 8. */
+int uic_fc_xe_train_step(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* batch, int32_t s_run,
+                         int32_t training, uint32_t seed, void* workspace, const float* inv_den, float* loss_out,
+                         const uic_fc_weights* grads, void* stream);
+/* The sampling pass of the self-critical step (P/trainer.py:167 -> FCModel_NMT._sample with sample_max = 0, :164-217, in TRAIN
+ * mode): multinomial draws, temperature and forced [N, L] tokens as uic_fc_sample; seq / seq_logp [N, L+1], S >= L + 1.
+ * LSTMCore's dropout (d->drop_p) is live on next_h of every core step t = 0 .. L with the masks uic_fc_forward(training = 1, seed)
+ * applies: site UIC_SITE_OUT0 + t, element index row * H + unit (uic_dropout_mask returns them).  The reference's quirks stay: the
+ * RAW sampled token feeds the next step, and the column at which every row has finished is not written, nor any behind it.
+ * The pass keeps its forward in the workspace in uic_fc_forward's layout (inputs, gates, cell and hidden states, f32 logits per
+ * step, the tokens fed): uic_fc_reward_backward on the SAME workspace, weights, batch, L and seed needs no second forward.
+ * Refused: a null pointer (forced may be NULL), L outside [1, S-1], temperature <= 0. */
+int uic_fc_sample_train(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* batch, int32_t L,
+                        float temperature, uint32_t seed, const int64_t* forced, void* workspace, int64_t* seq,
+                        float* seq_logp, void* stream);
+/* Backward of uic_fc_sample_train from RewardCriterion's gradient (P/misc/criterion.py:117-124, P/trainer.py:168-170):
+ * dlogp [N, L+1] = d loss / d seq_logp (uic_reward_criterion's dlogp times the upstream scalar).
+ * d logits[t, n, :] = dlogp[n, t] (onehot(token[n, t]) - softmax(logits[t, n, :])) for the columns the pass wrote, exact zeros
+ * behind them and wherever dlogp is 0 (behind a caption's first 0, whatever raw token was fed there) -- written in the operand
+ * dtype straight into the buffer the d h / dW GEMMs read; then the BPTT loop, the stacked weight-gradient GEMMs and the
+ * embedding backward of uic_fc_backward into `grads` (destination pointers, overwritten; no floating-point atomics).
+ * Refused: a null pointer, L outside [1, S-1]. */
+int uic_fc_reward_backward(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* batch, int32_t L,
+                           uint32_t seed, void* workspace, const float* dlogp, const uic_fc_weights* grads, void* stream);
 
 /* ---- pivot NMT step: NMTModel.forward + generator + NMTCriterion and their backward (P/models/NMT_Models.py:27-295,
  * 414-420; O = misc/OpenNMT-py-dalegebit/onmt: O/modules/StackedRNN.py:20-34, O/modules/GlobalAttention.py:112-167;

@@ -461,6 +461,12 @@ _SIGS = {
                                    C.c_int32, C.c_uint32, C.c_void_p, C.POINTER(NmtWeights), C.c_void_p]),
     "uic_fc_sample_beam": (C.c_int, [C.POINTER(FcDims), C.POINTER(FcWeights), C.POINTER(Batch), C.c_int32, C.c_int32, C.c_int32,
                                      C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uic_fc_xe_train_step": (C.c_int, [C.POINTER(FcDims), C.POINTER(FcWeights), C.POINTER(Batch), C.c_int32, C.c_int32, C.c_uint32,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(FcWeights), C.c_void_p]),
+    "uic_fc_sample_train": (C.c_int, [C.POINTER(FcDims), C.POINTER(FcWeights), C.POINTER(Batch), C.c_int32, C.c_float, C.c_uint32,
+                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "uic_fc_reward_backward": (C.c_int, [C.POINTER(FcDims), C.POINTER(FcWeights), C.POINTER(Batch), C.c_int32, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.POINTER(FcWeights), C.c_void_p]),
     "uic_nmt_translate_workspace_bytes": (C.c_size_t, [C.POINTER(NmtDims), C.c_int32, C.c_int32]),
     "uic_nmt_translate": (C.c_int, [C.POINTER(NmtDims), C.POINTER(NmtWeights), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p,
                                     C.c_void_p, C.c_void_p, C.c_void_p, C.POINTER(C.c_int32), C.c_void_p]),

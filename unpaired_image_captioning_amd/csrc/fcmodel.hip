@@ -5,6 +5,12 @@
 // (step 0 = img_embed(fc), step i = embed[labels[:, i-1]]), so i2h runs once over all S*N rows and only the
 // h2h GEMM (K = H) with the fused maxout-cell epilogue stays in the recurrence; the logit GEMM, log-softmax and
 // criterion run once over all rows; weight gradients are single GEMMs over the stacked rows.
+//
+// Training through the Trainer (P/trainer.py:141-173): uic_fc_xe_train_step is forward + criterion + backward in one call (the
+// same launches in the same order as the three calls).  The self-critical step's sampling pass (uic_fc_sample_train) is the
+// decode chain, but it writes every step into the teacher-forced layout above -- x_all, gates, c_buf, h_buf, the f32 logits of
+// each step, the raw tokens fed -- so that its backward (uic_fc_reward_backward) starts at RewardCriterion's gradient: the
+// criterion's row kernels turn d loss / d seq_logp into d logits in the operand dtype, and the tail of uic_fc_backward follows.
 #include "uic_common.h"
 #include "uic_host.h"
 #include "../../include/uic_hip.h"
@@ -36,6 +42,9 @@ struct FcLayout {
   float* bm_cand_val; int* bm_cand_idx; int64_t* bm_seq[2]; float* bm_lp[2]; float* bm_sum; int* bm_parent;
   int* bm_done_count; float* bm_done_p; int64_t* bm_done_seq; float* bm_done_lp;
   int* embed_scratch;   // uic_embed_bwd_sorted_launch
+  // kept sampling pass (uic_fc_sample_train -> uic_fc_reward_backward)
+  int64_t* tok;         // [N, S]: column j = the token fed at core step j + 1 (column 0 = <bos>), the layout of `labels`
+  float* scale;         // [N, S]: gradient weight of decision (n, t) for the criterion kernels
   size_t total;
 };
 
@@ -108,6 +117,8 @@ FcLayout fc_layout(const uic_fc_dims& d, const uic_fc_weights* w, void* ws) {
   L.bm_done_seq = (int64_t*)b.take(N * S * S * 8);
   L.bm_done_lp = (float*)b.take(N * S * S * 4);
   L.embed_scratch = (int*)b.take(uic_embed_bwd_sorted_scratch_ints((int)N, (int)S, d.V1, d.E) * 4);
+  L.tok = (int64_t*)b.take(N * S * 8);
+  L.scale = (float*)b.take(N * S * 4);
   L.total = (b.off + 255) & ~(size_t)255;
   return L;
 }
@@ -149,6 +160,73 @@ int fc_core(const uic_fc_dims& d, const FcLayout& L, const void* x, const uic_fc
   g.c_prev = c_prev; g.c_out = c_out; g.h_out = h_out; g.ldh = d.H; g.gates_out = gates_out;
   g.drop_p = drop_p; g.seed = seed; g.site = UIC_SITE_OUT0 + (unsigned)step;
   return uic_gemm_launch(g, s);
+}
+
+// Everything of the backward pass behind d logits [(s_run-1) N, V1p] (operand dtype, in L.dlogits): d h of the logit layer, the
+// logit layer's gradients, BPTT, the stacked core weight gradients, d x, the embedding table and img_embed.  `tokens`
+// [N, ld_tokens]: column j = the token fed at core step j + 1; fc_in: the features in the operand dtype.
+int fc_backward_tail(const uic_fc_dims* d, const FcLayout& L, const void* fc_in, const int64_t* tokens, int ld_tokens, int s_run,
+                     float drop_p, unsigned seed, const uic_fc_weights* G, hipStream_t s) {
+  const int dt = d->dtype, N = d->N, H = d->H, E = d->E, V1 = d->V1, V1p = (int)vpad(V1), H5 = 5 * H, Dfc = d->Dfc;
+  const size_t NH = (size_t)N * H;
+  const int Ml = (s_run - 1) * N, Ms = s_run * N;
+  {  // d h (logit path) for steps 1 .. s_run-1
+    UicGemmParams g = gemm_base(dt, Ml, H);
+    add_seg(g, L.dlogits, V1p, L.logit_wT, V1p, V1p);
+    g.C = L.dh_all; g.ldc = H; g.flags = UIC_GEMM_OUT_F32;
+    UIC_TRY(uic_gemm_launch(g, s));
+  }
+  {
+    const UicGemmTnSeg seg{off(L.h_buf, 2 * NH, dt), H, H};
+    const WDest d1{G->logit_w, H, 0, H};
+    UIC_TRY(wgrad_group(L.slab, L.slab_bytes, dt, L.dlogits, V1p, V1, &seg, 1, Ml, &d1, 1, s, false, L.tA, L.tB));
+  }
+  UIC_TRY(uic_colsum_launch(dt, L.dlogits, Ml, V1, V1p, G->logit_b, L.colscratch, L.colscratch_floats, s));
+  // BPTT
+  UIC_TRY(uic_fill_launch(L.dc, 0, NH * 4, s));
+  for (int t = s_run - 1; t >= 0; --t) {
+    UicLstmBwdParams p;
+    memset(&p, 0, sizeof(p));
+    p.dtype = dt; p.M = N; p.H = H;
+    if (t >= 1) { p.dh0 = L.dh_all + (size_t)(t - 1) * NH; p.lddh0 = H; }
+    if (t < s_run - 1) { p.dh1 = L.dhrec; p.lddh1 = H; }
+    p.drop_p = drop_p; p.seed = seed; p.site = UIC_SITE_OUT0 + (unsigned)t;
+    p.dc = L.dc; p.gates = off(L.gates, (size_t)t * N * H5, dt);
+    p.c_prev = L.c_buf + t * NH; p.c = L.c_buf + (t + 1) * NH;
+    p.dgates = offw(L.ds_all, (size_t)t * N * H5, dt);
+    UIC_TRY(uic_maxout_lstm_bwd_launch(p, s));
+    if (t > 0) {
+      UicGemmParams g = gemm_base(dt, N, H);
+      add_seg(g, off(L.ds_all, (size_t)t * N * H5, dt), H5, L.h2hT, H5, H5);
+      g.C = L.dhrec; g.ldc = H; g.flags = UIC_GEMM_OUT_F32;
+      UIC_TRY(uic_gemm_launch(g, s));
+    }
+  }
+  // core weights: dS^T [5H, S*N] x [h_prev | x]^T in one GEMM
+  {
+    const UicGemmTnSeg segs[2] = {{L.h_buf, H, H}, {L.x_all, E, E}};
+    const WDest dd[2] = {{G->h2h_w, H, 0, H}, {G->i2h_w, E, H, E}};
+    UIC_TRY(wgrad_group(L.slab, L.slab_bytes, dt, L.ds_all, H5, H5, segs, 2, Ms, dd, 2, s, false, L.tA, L.tB));
+  }
+  UIC_TRY(uic_colsum_launch(dt, L.ds_all, Ms, H5, H5, G->i2h_b, L.colscratch, L.colscratch_floats, s));
+  UIC_TRY(uic_copy_launch(G->h2h_b, G->i2h_b, (size_t)H5 * 4, s));
+  {  // d x for all steps
+    UicGemmParams g = gemm_base(dt, Ms, E);
+    add_seg(g, L.ds_all, H5, L.i2hT, H5, H5);
+    g.C = L.dx_all; g.ldc = E; g.flags = UIC_GEMM_OUT_F32;
+    UIC_TRY(uic_gemm_launch(g, s));
+  }
+  // (bucketed by word, one owner per table row: bit-reproducible, no floating-point atomics -- csrc/embedding.hip)
+  UIC_TRY(uic_embed_bwd_sorted_launch(dt, L.dx_all + (size_t)N * E, nullptr, tokens, ld_tokens, N, s_run - 1, V1, E, 0.f, -1, G->embed_w,
+                                      L.embed_scratch, s));
+  // img_embed from d x_0
+  UIC_TRY(uic_cast_f32_launch(dt, L.dx_all, L.dx0, (size_t)N * E, s));
+  {
+    const UicGemmTnSeg seg{fc_in, Dfc, Dfc};
+    const WDest d1{G->img_embed_w, Dfc, 0, Dfc};
+    UIC_TRY(wgrad_group(L.slab, L.slab_bytes, dt, L.dx0, E, E, &seg, 1, N, &d1, 1, s, false, L.tA, L.tB));
+  }
+  return uic_colsum_launch(UIC_F32, L.dx_all, N, E, E, G->img_embed_b, L.colscratch, L.colscratch_floats, s);
 }
 
 }  // namespace
@@ -244,70 +322,110 @@ int uic_fc_backward(const uic_fc_dims* d, const uic_fc_weights* w, const uic_top
   UIC_REQUIRE(!dlogprobs || logprobs, "fc_backward: dlogprobs needs the forward log-probs");
   hipStream_t s = (hipStream_t)stream;
   const FcLayout L = fc_layout(*d, w, workspace);
-  const int dt = d->dtype, N = d->N, H = d->H, E = d->E, V1 = d->V1, V1p = (int)vpad(V1), H5 = 5 * H, Dfc = d->Dfc;
-  const size_t NH = (size_t)N * H;
-  const float drop_p = training ? d->drop_p : 0.f;
-  const int Ml = (s_run - 1) * N, Ms = s_run * N;
+  const int dt = d->dtype, N = d->N, V1 = d->V1, V1p = (int)vpad(V1);
+  const int Ml = (s_run - 1) * N;
   const void* fc_in = dt == UIC_BF16 ? L.fcT : (const void*)b->fc_feats;
   if (dlogprobs)
     UIC_TRY(uic_logsoftmax_bwd_launch(dt, L.dlogits, Ml, V1, V1p, N, dlogprobs, (size_t)V1, (size_t)(d->S - 1) * V1, logprobs, s));
-  {  // d h (logit path) for steps 1 .. s_run-1
-    UicGemmParams g = gemm_base(dt, Ml, H);
-    add_seg(g, L.dlogits, V1p, L.logit_wT, V1p, V1p);
-    g.C = L.dh_all; g.ldc = H; g.flags = UIC_GEMM_OUT_F32;
-    UIC_TRY(uic_gemm_launch(g, s));
+  return fc_backward_tail(d, L, fc_in, b->labels, b->ld_labels, s_run, training ? d->drop_p : 0.f, seed, G, s);
+}
+
+int uic_fc_xe_train_step(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* b, int32_t s_run,
+                         int32_t training, uint32_t seed, void* workspace, const float* inv_den, float* loss_out,
+                         const uic_fc_weights* G, void* stream) {
+  // everything the three calls below would refuse is refused here, before the first of them has launched anything
+  UIC_TRY(fc_check(d));
+  UIC_REQUIRE(w && b && workspace && G && loss_out && b->fc_feats && b->labels && b->masks, "fc_xe_train_step: null pointer");
+  UIC_REQUIRE(s_run >= 2 && s_run <= d->S, "fc_xe_train_step: s_run=%d outside [2,%d]", s_run, d->S);
+  UIC_REQUIRE(b->ld_labels >= d->S && b->ld_masks >= d->S, "fc_xe_train_step: labels/masks need %d columns", d->S);
+  UIC_TRY(uic_fc_forward(d, w, b, s_run, training, seed, workspace, nullptr, stream));
+  UIC_TRY(uic_fc_xe_loss(d, b, s_run, workspace, inv_den, loss_out, stream));
+  UIC_TRY(uic_fc_backward(d, w, b, s_run, training, seed, workspace, nullptr, nullptr, G, stream));
+  // (sum(mask) of THIS batch, whatever denominator the caller handed in: uic_fc_xe_loss left it in the workspace)
+  return uic_copy_launch(loss_out + 1, fc_layout(*d, nullptr, workspace).scalars, 4, (hipStream_t)stream);
+}
+
+int uic_fc_sample_train(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* b, int32_t Lsteps,
+                        float temperature, uint32_t seed, const int64_t* forced, void* workspace, int64_t* seq,
+                        float* seq_logp, void* stream) {
+  UIC_TRY(fc_check(d));
+  UIC_REQUIRE(w && b && workspace && seq && seq_logp && b->fc_feats, "fc_sample_train: null pointer");
+  UIC_REQUIRE(Lsteps >= 1 && Lsteps + 1 <= d->S, "fc_sample_train: L=%d needs S >= %d", Lsteps, Lsteps + 1);
+  UIC_REQUIRE(temperature > 0.f, "fc_sample_train: temperature must be positive");
+  hipStream_t s = (hipStream_t)stream;
+  const FcLayout L = fc_layout(*d, w, workspace);
+  const int dt = d->dtype, N = d->N, H = d->H, E = d->E, V1 = d->V1, V1p = (int)vpad(V1), H5 = 5 * H, S = d->S;
+  const size_t Sz = uic_dtype_size(dt), NH = (size_t)N * H, NE = (size_t)N * E;
+  UIC_TRY(fc_refresh(*d, w, L, s));
+  const void* fc_in = b->fc_feats;
+  if (dt == UIC_BF16) {
+    UIC_TRY(uic_cast_f32_launch(dt, b->fc_feats, L.fcT, (size_t)N * d->Dfc, s));
+    fc_in = L.fcT;
   }
-  {
-    const UicGemmTnSeg seg{off(L.h_buf, 2 * NH, dt), H, H};
-    const WDest d1{G->logit_w, H, 0, H};
-    UIC_TRY(wgrad_group(L.slab, L.slab_bytes, dt, L.dlogits, V1p, V1, &seg, 1, Ml, &d1, 1, s, false, L.tA, L.tB));
-  }
-  UIC_TRY(uic_colsum_launch(dt, L.dlogits, Ml, V1, V1p, G->logit_b, L.colscratch, L.colscratch_floats, s));
-  // BPTT
-  UIC_TRY(uic_fill_launch(L.dc, 0, NH * 4, s));
-  for (int t = s_run - 1; t >= 0; --t) {
-    UicLstmBwdParams p;
-    memset(&p, 0, sizeof(p));
-    p.dtype = dt; p.M = N; p.H = H;
-    if (t >= 1) { p.dh0 = L.dh_all + (size_t)(t - 1) * NH; p.lddh0 = H; }
-    if (t < s_run - 1) { p.dh1 = L.dhrec; p.lddh1 = H; }
-    p.drop_p = drop_p; p.seed = seed; p.site = UIC_SITE_OUT0 + (unsigned)t;
-    p.dc = L.dc; p.gates = off(L.gates, (size_t)t * N * H5, dt);
-    p.c_prev = L.c_buf + t * NH; p.c = L.c_buf + (t + 1) * NH;
-    p.dgates = offw(L.ds_all, (size_t)t * N * H5, dt);
-    UIC_TRY(uic_maxout_lstm_bwd_launch(p, s));
-    if (t > 0) {
-      UicGemmParams g = gemm_base(dt, N, H);
-      add_seg(g, off(L.ds_all, (size_t)t * N * H5, dt), H5, L.h2hT, H5, H5);
-      g.C = L.dhrec; g.ldc = H; g.flags = UIC_GEMM_OUT_F32;
+  // the teacher-forced layout of uic_fc_forward, filled step by step: x_all[t], gates[t], c_buf[t+1], h_buf[t+1] (dropped), the
+  // logits of core step t >= 1 in rows (t-1) N .., and the token fed at step t >= 1 in tok[:, t-1]
+  UIC_TRY(uic_fill_launch(L.h_buf, 0, NH * Sz, s));
+  UIC_TRY(uic_fill_launch(L.c_buf, 0, NH * 4, s));
+  UIC_TRY(uic_fill_launch(L.tok, 0, (size_t)N * S * 8, s));         // column 0: <bos> at step 1 (:183-184)
+  UIC_TRY(uic_fill_launch(L.s_it, 0, (size_t)N * 8, s));
+  UIC_TRY(uic_fill_launch(L.s_unf, 0, (size_t)N * 4, s));
+  UIC_TRY(uic_fill_launch(L.s_nunf, 0, (size_t)(S + 2) * UIC_NUNF_STRIPES * 4, s));
+  const int ld = Lsteps + 1;                                         // seq / seqLogprobs are [N, L+1] (:176-177)
+  UIC_TRY(uic_fill_launch(seq, 0, (size_t)N * ld * 8, s));
+  UIC_TRY(uic_fill_launch(seq_logp, 0, (size_t)N * ld * 4, s));
+  for (int t = 0; t <= Lsteps; ++t) {                                // core steps 0 .. L; decisions after steps 1 .. L
+    void* xt = offw(L.x_all, (size_t)t * NE, dt);
+    if (t == 0) {
+      UicGemmParams g = gemm_base(dt, N, E);
+      add_seg(g, fc_in, d->Dfc, L.img_w, d->Dfc, d->Dfc);
+      g.C = xt; g.ldc = E; g.bias = w->img_embed_b;
       UIC_TRY(uic_gemm_launch(g, s));
+    } else {
+      UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.s_it, 1, N, 1, 0.f, 0, 0, 0, 0, xt, s));
+    }
+    // LSTMCore.dropout on next_h (:47-50) is live in train mode: the masks of uic_fc_forward(training = 1, seed)
+    UIC_TRY(fc_core(*d, L, xt, w, nullptr, off(L.h_buf, t * NH, dt), L.c_buf + t * NH, L.c_buf + (t + 1) * NH,
+                    offw(L.h_buf, (t + 1) * NH, dt), offw(L.gates, (size_t)t * N * H5, dt), d->drop_p, seed, t, s));
+    if (t >= 1) {
+      float* logits = L.logits + (size_t)(t - 1) * N * V1p;
+      UicGemmParams g = gemm_base(dt, N, V1);
+      add_seg(g, off(L.h_buf, (t + 1) * NH, dt), H, L.logit_w, H, H);
+      g.C = logits; g.ldc = V1p; g.bias = w->logit_b; g.flags = UIC_GEMM_OUT_F32;
+      UIC_TRY(uic_gemm_launch(g, s));
+      UicSampleParams p;
+      memset(&p, 0, sizeof(p));
+      p.dtype = dt; p.N = N; p.V1 = V1; p.ldv = V1p; p.t = t - 1; p.L = Lsteps;
+      p.logits = logits; p.sample_max = 0; p.temperature = temperature; p.seed = seed;
+      p.seq = seq; p.seq_logp = seq_logp; p.it = L.s_it; p.unfinished = L.s_unf; p.n_unfinished = L.s_nunf;
+      p.forced = forced; p.fc_mode = 1; p.ld_out = ld;
+      UIC_TRY(uic_sample_step_launch(p, s));
+      // the RAW choice: what the next step is fed (:199) and what this step's log-prob was gathered at
+      UIC_TRY(uic_copy_tokens_launch(L.s_it, 1, N, 1, L.tok + t, S, s));
     }
   }
-  // core weights: dS^T [5H, S*N] x [h_prev | x]^T in one GEMM
-  {
-    const UicGemmTnSeg segs[2] = {{L.h_buf, H, H}, {L.x_all, E, E}};
-    const WDest dd[2] = {{G->h2h_w, H, 0, H}, {G->i2h_w, E, H, E}};
-    UIC_TRY(wgrad_group(L.slab, L.slab_bytes, dt, L.ds_all, H5, H5, segs, 2, Ms, dd, 2, s, false, L.tA, L.tB));
-  }
-  UIC_TRY(uic_colsum_launch(dt, L.ds_all, Ms, H5, H5, G->i2h_b, L.colscratch, L.colscratch_floats, s));
-  UIC_TRY(uic_copy_launch(G->h2h_b, G->i2h_b, (size_t)H5 * 4, s));
-  {  // d x for all steps
-    UicGemmParams g = gemm_base(dt, Ms, E);
-    add_seg(g, L.ds_all, H5, L.i2hT, H5, H5);
-    g.C = L.dx_all; g.ldc = E; g.flags = UIC_GEMM_OUT_F32;
-    UIC_TRY(uic_gemm_launch(g, s));
-  }
-  // (bucketed by word, one owner per table row: bit-reproducible, no floating-point atomics -- csrc/embedding.hip)
-  UIC_TRY(uic_embed_bwd_sorted_launch(dt, L.dx_all + (size_t)N * E, nullptr, b->labels, b->ld_labels, N, s_run - 1, V1, E, 0.f, -1, G->embed_w,
-                                      L.embed_scratch, s));
-  // img_embed from d x_0
-  UIC_TRY(uic_cast_f32_launch(dt, L.dx_all, L.dx0, (size_t)N * E, s));
-  {
-    const UicGemmTnSeg seg{fc_in, Dfc, Dfc};
-    const WDest d1{G->img_embed_w, Dfc, 0, Dfc};
-    UIC_TRY(wgrad_group(L.slab, L.slab_bytes, dt, L.dx0, E, E, &seg, 1, N, &d1, 1, s, false, L.tA, L.tB));
-  }
-  return uic_colsum_launch(UIC_F32, L.dx_all, N, E, E, G->img_embed_b, L.colscratch, L.colscratch_floats, s);
+  return uic_sample_fixup_launch(N, Lsteps, ld, L.s_nunf, seq, seq_logp, s);
+}
+
+int uic_fc_reward_backward(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* b, int32_t Lsteps,
+                           uint32_t seed, void* workspace, const float* dlogp, const uic_fc_weights* G, void* stream) {
+  UIC_TRY(fc_check(d));
+  UIC_REQUIRE(w && b && workspace && dlogp && G && b->fc_feats, "fc_reward_backward: null pointer");
+  UIC_REQUIRE(Lsteps >= 1 && Lsteps + 1 <= d->S, "fc_reward_backward: L=%d needs S >= %d", Lsteps, Lsteps + 1);
+  hipStream_t s = (hipStream_t)stream;
+  const FcLayout L = fc_layout(*d, w, workspace);
+  const int dt = d->dtype, N = d->N, V1 = d->V1, V1p = (int)vpad(V1), S = d->S, ld = Lsteps + 1;
+  const void* fc_in = dt == UIC_BF16 ? L.fcT : (const void*)b->fc_feats;
+  UIC_TRY(uic_sample_reward_scale_launch(N, Lsteps, ld, L.s_nunf, dlogp, L.scale, s));
+  // d logits of decision t (core step t + 1) = (softmax - onehot(tok[:, t + 1])) * scale[:, t], straight into the operand-dtype
+  // buffer the d h / dW GEMMs read: the criterion's row kernels with a per-position weight
+  UicXeParams x;
+  memset(&x, 0, sizeof(x));
+  x.dtype = dt; x.M = Lsteps * N; x.V1 = V1; x.ldv = V1p; x.logits = L.logits; x.dlogits = L.dlogits; x.N = N;
+  x.target = L.tok; x.ldtarget = S; x.target_col0 = 1;
+  x.grad_scale = L.scale; x.ldscale = ld; x.scale_col0 = 0;
+  x.row_loss = L.row_loss; x.write_grad = 1;
+  UIC_TRY(uic_xe_launch(x, s));
+  return fc_backward_tail(d, L, fc_in, L.tok, S, Lsteps + 1, d->drop_p, seed, G, s);
 }
 
 int uic_fc_sample(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* b, int32_t Lsteps,

@@ -240,6 +240,23 @@ __global__ void sample_fixup_kernel(int N, int L, int ld, const int* n_unfinishe
   }
 }
 
+// The gradient weights of a kept FCModel_NMT sampling pass (uic_fc_reward_backward): d logits[t, n, :] =
+// dlogp[n, t] (onehot - softmax) = (softmax - onehot) * scale[n, t] with scale = -dlogp for the steps the pass ran.  The
+// reference never wrote the column at which every row had finished, nor anything behind it (:203-206) -- seqLogprobs is a
+// constant 0 there -- so those columns weigh +0, like every position whose dlogp is 0 (behind a caption's end).
+__global__ void sample_reward_scale_kernel(int N, int L, int ld, const int* n_unfinished, const float* dlogp, float* scale) {
+  int first = L;
+  for (int t = 0; t < L; ++t) {
+    int live = 0;
+    for (int k = 0; k < UIC_NUNF_STRIPES; ++k) live += n_unfinished[t * UIC_NUNF_STRIPES + k];
+    if (live == 0) { first = t; break; }
+  }
+  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < N * ld; i += gridDim.x * blockDim.x) {
+    const float g = dlogp[i];
+    scale[i] = (i % ld >= first || g == 0.f) ? 0.f : -g;
+  }
+}
+
 }  // namespace
 
 int uic_ss_sample_launch(const float* logits_prev, int N, int V1, int ldv, const int64_t* labels, int ld_labels, int t,
@@ -273,5 +290,11 @@ int uic_sample_step_launch(const UicSampleParams& p, hipStream_t s) {
 int uic_sample_fixup_launch(int N, int L, int ld, const int* n_unfinished, int64_t* seq, float* seq_logp, hipStream_t s) {
   hipLaunchKernelGGL(sample_fixup_kernel, dim3(8), dim3(NT), 0, s, N, L, ld, n_unfinished, seq, seq_logp);
   UIC_LAUNCH_CHECK("sample_fixup");
+  return UIC_OK;
+}
+int uic_sample_reward_scale_launch(int N, int L, int ld, const int* n_unfinished, const float* dlogp, float* scale, hipStream_t s) {
+  UIC_REQUIRE(n_unfinished && dlogp && scale && L <= ld, "sample_reward_scale: bad arguments");
+  hipLaunchKernelGGL(sample_reward_scale_kernel, dim3(8), dim3(NT), 0, s, N, L, ld, n_unfinished, dlogp, scale);
+  UIC_LAUNCH_CHECK("sample_reward_scale");
   return UIC_OK;
 }

@@ -803,6 +803,9 @@ struct UicSampleParams {
 int uic_sample_step_launch(const UicSampleParams& p, hipStream_t s);
 // FCModel_NMT._sample: clears the column at which every row had finished and everything after it
 int uic_sample_fixup_launch(int N, int L, int ld, const int* n_unfinished, int64_t* seq, float* seq_logp, hipStream_t s);
+// the gradient weights of that pass for uic_xe_launch's grad_scale: scale[n, t] = -dlogp[n, t] in front of the column the fix-up
+// cleared, +0 from there on and wherever dlogp is 0; dlogp / scale [N, ld], L <= ld decision columns
+int uic_sample_reward_scale_launch(int N, int L, int ld, const int* n_unfinished, const float* dlogp, float* scale, hipStream_t s);
 // ---- beam search bookkeeping (beam.hip): rows = (image, beam)
 #define UIC_BEAM_MAX 16
 struct UicBeamParams {

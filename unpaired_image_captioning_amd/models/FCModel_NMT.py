@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
+from .AttModel import _HeldWorkspace
 from .CaptionModel import CaptionModel
 from .. import _lib
 from .._lib import Batch, FcDims, FcWeights, FC_WEIGHT_FIELDS, check, ptr, stream
@@ -28,6 +29,8 @@ class LSTMCore(nn.Module):
 
 
 class _FcEngine(object):
+    recurrence = 0      # (Trainer sets the TopDown engine's launch-mode bits on whatever engine it is given; nothing here reads them)
+
     def __init__(self, model):
         self.lib = _lib.load()
         self.m = model
@@ -69,6 +72,66 @@ class _FcEngine(object):
         b.ld_masks = masks.shape[1] if masks is not None else 0
         return b
 
+    def token_steps(self, labels):
+        """The step count trainer.xe_step passes on: decode steps as AttModel counts them = core steps - 1 (the image step)."""
+        return self.m._steps_to_run(labels) - 1
+
+    def xe_train_step(self, params, fc, att, att_masks, labels, masks, t_run, training, seed, grads, inv_den=None,
+                      grad_scale=None, ss_prob=0.0, keep_workspace=False, d_fc=None, d_att=None, resume_ws=None, out=None, live=None):
+        """trainer.xe_step's call on a TopDownEngine, for this model: uic_fc_xe_train_step (forward + LanguageModelCriterion +
+        backward, one library call); returns a device tensor [loss, sum(mask)].  t_run counts decode steps (core steps - 1).
+        att / att_masks / live mean nothing to a model without attention and are ignored; what would change the result is
+        refused."""
+        if ss_prob:
+            raise NotImplementedError("FCModel_NMT scheduled sampling is broken in the reference (P/models/FCModel_NMT.py:108); not provided")
+        if d_fc is not None or d_att is not None:
+            raise NotImplementedError("FCModel_NMT: gradients w.r.t. the input features are not built")
+        if grad_scale is not None or resume_ws is not None or keep_workspace:
+            raise NotImplementedError("FCModel_NMT: the self-critical step goes through sample_train / reward_backward")
+        if masks is None:
+            raise ValueError("FCModel_NMT.xe_train_step needs the masks")
+        fc = fc.contiguous().float()
+        labels = labels.contiguous()
+        masks = masks.contiguous().float()
+        d = self.dims(fc.shape[0], labels.shape[1])
+        ws = self.workspace(d, fc.device)
+        w, g, b = self.weights(params), self.weights(grads), self.batch(fc, labels, masks)
+        if out is None:
+            out = torch.empty(2, dtype=torch.float32, device=fc.device)
+        try:
+            check(self.lib.uic_fc_xe_train_step(C.byref(d), C.byref(w), C.byref(b), int(t_run) + 1, int(bool(training)),
+                                                seed & 0xFFFFFFFF, ptr(ws), ptr(inv_den), ptr(out), C.byref(g), stream()),
+                  "fc_xe_train_step")
+        finally:
+            self.release(d, ws)
+        return out
+
+    def sample_train(self, params, fc, L, temperature=1.0, seed=0, forced=None):
+        """The train-mode sampling pass (uic_fc_sample_train): (seq, seq_logp [N, L+1], d, ws) with the workspace still checked
+        out -- it holds the whole forward pass for reward_backward."""
+        N = fc.shape[0]
+        d = self.dims(N, L + 2)
+        ws = self.workspace(d, fc.device)
+        seq = torch.zeros(N, L + 1, dtype=torch.int64, device=fc.device)
+        lp = torch.zeros(N, L + 1, dtype=torch.float32, device=fc.device)
+        w, b = self.weights(params), self.batch(fc)
+        try:
+            check(self.lib.uic_fc_sample_train(C.byref(d), C.byref(w), C.byref(b), L, float(temperature), seed & 0xFFFFFFFF,
+                                               ptr(forced), ptr(ws), ptr(seq), ptr(lp), stream()), "fc_sample_train")
+        except BaseException:
+            self.release(d, ws)
+            raise
+        return seq, lp, d, ws
+
+    def reward_backward(self, params, fc, L, seed, d, ws, dlogp, grads):
+        """Backward of sample_train's pass from d loss / d seq_logp [N, L+1] into `grads`; releases the workspace."""
+        w, g, b = self.weights(params), self.weights(grads), self.batch(fc)
+        try:
+            check(self.lib.uic_fc_reward_backward(C.byref(d), C.byref(w), C.byref(b), L, seed & 0xFFFFFFFF, ptr(ws),
+                                                  ptr(dlogp), C.byref(g), stream()), "fc_reward_backward")
+        finally:
+            self.release(d, ws)
+
 
 class _FcForward(torch.autograd.Function):
     @staticmethod
@@ -108,7 +171,54 @@ class _FcForward(torch.autograd.Function):
         return (None, None, None, None) + tuple(grads[k] for k in model.param_names)
 
 
+class _PoolSlot(object):
+    """What _HeldWorkspace releases into: this engine's pool files a workspace under its dims."""
+
+    def __init__(self, eng, d):
+        self.eng, self.d = eng, d
+
+    def release(self, ws):
+        self.eng.release(self.d, ws)
+
+
+class _FcSample(torch.autograd.Function):
+    """Multinomial sampling pass of the self-critical step (P/trainer.py:167) in train mode: returns (seq, seqLogprobs) with
+    seqLogprobs differentiable.  The pass keeps its forward in its workspace; backward starts at RewardCriterion's gradient
+    (uic_fc_reward_backward) -- no second forward, no dense [N, L, V+1] gradient."""
+
+    @staticmethod
+    def forward(ctx, model, fc, temperature, forced, *params):
+        eng = model.engine
+        pd = dict(zip(model.param_names, params))
+        seed = model.next_seed()
+        seq, lp, d, ws = eng.sample_train(pd, fc, model.seq_length, temperature, seed, forced)
+        ctx.ws = _HeldWorkspace(_PoolSlot(eng, d), ws)     # back to the pool after backward, or when the graph is dropped
+        ctx.model, ctx.d, ctx.seed, ctx.fc = model, d, seed, fc
+        ctx.params = params
+        ctx.mark_non_differentiable(seq)
+        return seq, lp
+
+    @staticmethod
+    def backward(ctx, g_seq, g_lp):
+        model = ctx.model
+        ws = ctx.ws.take() if ctx.ws is not None else None
+        if ws is None:
+            raise RuntimeError("FCModel_NMT: a second backward over one sampling pass -- its kept forward was released by the first")
+        pd = dict(zip(model.param_names, ctx.params))
+        # direct: every p.grad IS its view of the optimizer's flat gradient arena (Trainer.train_self_critical set both up)
+        sink = getattr(model, '_grad_sink', None)
+        direct = sink is not None and all(p.grad is sink[k] for k, p in zip(model.param_names, ctx.params))
+        grads = sink if direct else {k: torch.empty_like(v) for k, v in pd.items()}
+        model.engine.reward_backward(pd, ctx.fc, model.seq_length, ctx.seed, ctx.d, ws, g_lp.contiguous().float(), grads)
+        if direct:
+            return (None, None, None, None) + (None,) * len(model.param_names)
+        return (None, None, None, None) + tuple(grads[k] for k in model.param_names)
+
+
 class FCModel_NMT(CaptionModel):
+    supports_grad_sink = True      # _FcSample.backward can write straight into Trainer's flat gradient arena
+    uses_att_feats = False         # Trainer: the batch's rows are fc_feats' rows
+
     def __init__(self, opt):
         super(FCModel_NMT, self).__init__()
         self.vocab_size = opt.vocab_size
@@ -171,7 +281,13 @@ class FCModel_NMT(CaptionModel):
                                       "batch, P/models/FCModel_NMT.py:108); not provided")
         s_run = self._steps_to_run(seq)
         params = [self.param_dict()[k] for k in self.param_names]
-        return _FcForward.apply(self, fc_feats.contiguous().float(), seq.contiguous(), s_run, *params)
+        fc = fc_feats.contiguous().float()
+        if fc.shape[0] != seq.shape[0]:
+            # features once per image, several captions each (the loader's validation batches, eval_utils.eval_split)
+            if fc.shape[0] == 0 or seq.shape[0] % fc.shape[0]:
+                raise ValueError("FCModel_NMT: %d caption rows for %d feature rows" % (seq.shape[0], fc.shape[0]))
+            fc = fc.repeat_interleave(seq.shape[0] // fc.shape[0], 0).contiguous()
+        return _FcForward.apply(self, fc, seq.contiguous(), s_run, *params)
 
     def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
         """FCModel_NMT._sample_beam (P/models/FCModel_NMT.py:136-162) over CaptionModel.beam_search, all images in one
@@ -215,6 +331,10 @@ class FCModel_NMT(CaptionModel):
         eng = self.engine
         fc = fc_feats.contiguous().float()
         N, L = fc.shape[0], self.seq_length
+        if self.training and torch.is_grad_enabled() and not opt.get('sample_max', 1):
+            # the self-critical step's pass (P/trainer.py:167): train mode, so LSTMCore's dropout is live, and differentiable
+            params = [self.param_dict()[k] for k in self.param_names]
+            return _FcSample.apply(self, fc, float(opt.get('temperature', 1.0)), opt.get('forced_tokens'), *params)
         d = eng.dims(N, L + 2)
         ws = eng.workspace(d, fc.device)
         seq = torch.zeros(N, L + 1, dtype=torch.int64, device=fc.device)

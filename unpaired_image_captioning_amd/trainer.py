@@ -37,7 +37,8 @@ def xe_step(model, batch, t_run=None, inv_den=None, grads=None, return_seed=Fals
     eng = model.engine
     labels = batch["labels"]
     if t_run is None:
-        t_run = model._steps_to_run(labels)
+        # (decode steps; FCModel_NMT's own count includes its image step, its engine translates)
+        t_run = eng.token_steps(labels) if hasattr(eng, 'token_steps') else model._steps_to_run(labels)
     pd = {k: v.detach() for k, v in model.param_dict().items()}
     seed = model.next_seed()
     training = model.training
@@ -48,7 +49,7 @@ def xe_step(model, batch, t_run=None, inv_den=None, grads=None, return_seed=Fals
         if grads is None:
             grads = {k: torch.empty_like(v) for k, v in pd.items()}
         live = (batch.get("live_rows"), batch["live_count"], batch.get("unfinished_count")) if batch.get("live_count") is not None else None
-        out = eng.xe_train_step(pd, batch["fc_feats"], batch["att_feats"], batch.get("att_masks"), labels, batch["masks"],
+        out = eng.xe_train_step(pd, batch["fc_feats"], batch.get("att_feats"), batch.get("att_masks"), labels, batch["masks"],
                                 t_run, training, seed, grads, inv_den, ss_prob=ss_prob, d_fc=d_fc, d_att=d_att, out=out, live=live)
         if return_seed:
             return out[0], grads, seed
@@ -653,9 +654,11 @@ class Trainer(object):
             self.build_optimizer()
         batch = self._device_batch(data)
         model = self.i2t_model
-        fc, att, am = batch["fc_feats"], batch["att_feats"], batch.get("att_masks")
-        n_rows = len(data["labels"]) if data.get("labels") is not None else att.shape[0]
-        S = n_rows // att.shape[0]                        # > 1 when to_device shipped every image once
+        fc, att, am = batch["fc_feats"], batch.get("att_feats"), batch.get("att_masks")
+        # (a model without attention features -- the `fc` captioner -- counts its rows in fc_feats)
+        feat_rows = att.shape[0] if att is not None and getattr(model, 'uses_att_feats', True) else fc.shape[0]
+        n_rows = len(data["labels"]) if data.get("labels") is not None else feat_rows
+        S = n_rows // feat_rows                           # > 1 when to_device shipped every image once
         import contextlib
         eng = getattr(model, 'engine', None)
         try:
