@@ -48,9 +48,12 @@ def rounded(t, dt):
 
 
 @pytest.mark.parametrize("dt", [0, 1])
-@pytest.mark.parametrize("shape", [(70, 51, 72), (640, 512, 512), (129, 200, 40), (1, 8, 8), (2304, 96, 2048)])
+@pytest.mark.parametrize("shape", [(70, 51, 72), (640, 512, 512), (129, 200, 40), (1, 8, 8), (2304, 96, 2048), (64, 40, 1024), (1800, 1800, 72)])
 @pytest.mark.parametrize("flags", [0, 1, 4, 6])
 def test_linear(dt, shape, flags):
+    """The last two shapes reach the two tiles of csrc/gemm_skinny.hip that nothing else in this module launches: (64, 40, 1024)
+    the 8-way in-block K split (one row tile, K * 2 B = 2048), (1800, 1800, 72) the 128 x 128 register-staged tile (225 blocks of
+    128 x 128, K not a whole LDS-DMA round in either dtype)."""
     L = _lib()
     lib = L.load()
     M, N, K = shape
@@ -482,7 +485,7 @@ def test_adam_step_matches_oracle():
 @pytest.mark.parametrize("dtype", ["bf16", "f32"])
 @pytest.mark.parametrize("M,N,K,S", [(640, 1536, 2048, 4), (640, 1024, 2048, 4), (640, 512, 2048, 8), (600, 1000, 1024, 2), (128, 128, 512, 1)])
 def test_linear_partials_slices_add_up_to_the_product_and_repeat_bit_for_bit(dtype, M, N, K, S):
-    """uic_linear_partials (the BPTT loop's split-K d x GEMMs, csrc/gemm.hip: LDS-DMA staging ordered by hand-placed vmcnt waits
+    """uic_linear_partials (the BPTT loop's split-K d x GEMMs, csrc/gemm_glds.hip: LDS-DMA staging ordered by hand-placed vmcnt waits
     and raw barriers): the slices add up to the product, and 30 launches beside an HBM-bound neighbour on another stream all give
     the first launch's bits (a wait that is one round short shows up as a result that depends on timing).  Round 6 also tried a
     ring of four staging buffers for these launches: same bits, same 13.4 us -- their time is MFMA issue (3.9 us per wave),

@@ -2,7 +2,7 @@
 the row sits, and a value that is dropped by a select leaves no trace, so every comparison here is bit for bit:
   * uic_live_order (csrc/live_rows.hip): caption lengths, their stable descending order, its inverse and the per-step counts
     against numpy, and the status word for counts that are not the masks';
-  * uic_linear_partials_rows (csrc/gemm.hip, the slab epilogue with a row map): a compact A operand whose tile tail holds NaN, the
+  * uic_linear_partials_rows (csrc/gemm_glds.hip, the slab epilogue with a row map): a compact A operand whose tile tail holds NaN, the
     written slab rows against the unmapped launch, the others against a sentinel;
   * uic_lstm_cell_bwd_live / uic_h2att_cell_bwd_live (csrc/lstm_cell.hip, csrc/bptt_fused.hip): slab rows of ended captions filled
     with NaN against the same rows zeroed, against the operators without row_len, and the compact copy against the rows by order."""

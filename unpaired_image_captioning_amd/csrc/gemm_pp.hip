@@ -45,12 +45,11 @@
 // which a separate 283 MB cast pass used to make.  vmcnt counts loads, stores and LDS-DMA together in issue order, so every
 // even phase waits vmcnt(4 + nA + nS): the ops younger than the unit being committed are two B units (2 DMA each), one A unit
 // (nA loads) and the previous commit's nS copy stores.
-#include "uic_common.h"
-#include <type_traits>
+#include "gemm_internal.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4pp;
+using gemm::u32x4;
 
 #define PP_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
@@ -73,20 +72,13 @@ __global__ __launch_bounds__(512) void uic_gemm_pp_kernel(const UicGemmParams p)
   {
     const int gx = gridDim.x, gy = gridDim.y, nblk = gx * gy;
     const int lin = blockIdx.x + gx * blockIdx.y;
-    const int q = nblk >> 3, r = nblk & 7, xcd = lin & 7, idx = lin >> 3;
-    const int lp = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    constexpr int GM = 8;
-    const int width = GM * gy;
-    const int first = (lp / width) * GM;
-    const int gsz = min(gx - first, GM);
-    const int rem = lp % width;
-    bm = first + rem % gsz;
-    bn = rem / gsz;
+    gemm::grouped_tile(gemm::xcd_run(lin, nblk), gx, gy, bm, bn);
   }
   const int m0 = bm * BM, n0 = bn * 256;
   const UicGemmSeg sg = p.seg[0];
 
-  // K tiles of this workgroup: all of them, or slice blockIdx.z of a split-K launch (an even number each; launch_pp checks)
+  // K tiles of this workgroup: all of them, or slice blockIdx.z of a split-K launch (an even number each; launch_pp checks).
+  // Written out, not gemm::splitk_slice's exact-division sibling: as a function it changed this kernel's instruction streams.
   int kt0 = 0, nt = sg.K / 64;
   if (p.splitk > 1) {
     const int tps = nt / p.splitk;
@@ -131,9 +123,7 @@ __global__ __launch_bounds__(512) void uic_gemm_pp_kernel(const UicGemmParams p)
       }
       dstB[s][j] = ABYTES + (unsigned)(((qb >> 2) * 64 + s * 32 + (qb & 3) * 8) * 128);
     }
-#define PP_GLDS(SRC, DST)                                                                                   \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(SRC),                   \
-                                   (__attribute__((address_space(3))) void*)(smem + (DST)), 16, 0, 0)
+#define PP_GLDS(SRC, DST) gemm::dma16(SRC, smem + (DST))
 #define PP_STAGE_A(S, BUF)                                                                                   \
   do {                                                                                                      \
     PP_GLDS(srcA[S][0], dstA[S][0] + (BUF) * BUFB); srcA[S][0] += 128;                                      \
@@ -158,15 +148,15 @@ __global__ __launch_bounds__(512) void uic_gemm_pp_kernel(const UicGemmParams p)
 #define PP_COMMIT1(S, J, BUF, CP)                                                                                               \
   do {                                                                                                                          \
     asm volatile("" : "+v"(ra[S][J][0]), "+v"(ra[S][J][1]));                                                                     \
-    u32x4pp pk;                                                                                                                 \
+    u32x4 pk;                                                                                                                 \
     pk[0] = uic_pack_bf16x2(ra[S][J][0][0], ra[S][J][0][1]); pk[1] = uic_pack_bf16x2(ra[S][J][0][2], ra[S][J][0][3]);             \
     pk[2] = uic_pack_bf16x2(ra[S][J][1][0], ra[S][J][1][1]); pk[3] = uic_pack_bf16x2(ra[S][J][1][2], ra[S][J][1][3]);             \
-    *(__attribute__((address_space(3))) u32x4pp*)(size_t)(wrA[S][J] + (unsigned)(BUF) * BUFB) = pk;   /* (compiler-visible too) */  \
+    *(__attribute__((address_space(3))) u32x4*)(size_t)(wrA[S][J] + (unsigned)(BUF) * BUFB) = pk;   /* (compiler-visible too) */  \
     /* (a compiler-visible store: as inline asm the machine does not know that pk is VMEM store data and lets the next piece's */ \
     /* conversions overwrite the registers while the store still reads them -- 32-64 wrong elements in 1 % of the launches     */ \
     /* beside a busy neighbour, found by a soak; the asm statements around it carry memory clobbers, so it stays in place and  */ \
     /* counts in vmcnt exactly where the waits expect it)                                                                      */ \
-    if (CP) *(u32x4pp*)((char*)baseC + offC[S][J]) = pk;                                                                        \
+    if (CP) *(u32x4*)((char*)baseC + offC[S][J]) = pk;                                                                        \
     offC[S][J] += 128;                                                                                                          \
   } while (0)
   // (the wait is the caller's: PP_WAIT_A / PP_VMCNT)
@@ -204,7 +194,7 @@ __global__ __launch_bounds__(512) void uic_gemm_pp_kernel(const UicGemmParams p)
   for (int i = 0; i < 2 * RT; ++i)
 #pragma unroll
     for (int j = 0; j < 4; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  u32x4pp a[4][2], b0[2][2], b1[2][2];
+  u32x4 a[4][2], b0[2][2], b1[2][2];
 
 #define PP_READ_A(S, AD)                                                                                    \
   do {                                                                                                      \

@@ -14,16 +14,14 @@
 //    DMA writes LDS lane-linearly, so the XOR is applied on the SOURCE side: lane (row, slot) fetches chunk slot ^ f(row).
 //  * B may be up to 4 column segments living in different matrices ([ctx | h_att | h_lang] of the LSTM weight
 //    gradients): torch.cat is never materialised on this side either.
-//  * Output: raw f32 partial tiles into slab[z][M][N] (split-K over blockIdx.z); uic_splitk_reduce_launch sums the
+//  * Output: raw f32 partial tiles into slab[z][M][N] (split-K over blockIdx.z); splitk_reduce.hip sums the
 //    slices in a fixed order and scatters column ranges to their destinations (deterministic).
-#include "uic_common.h"
-#include <type_traits>
-#include <stdlib.h>
+#include "gemm_internal.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4v;
+using gemm::u32x4;
 
 // NS = LDS stages (32 KB each).  2: one K round in flight behind the one being multiplied, two workgroups per CU.  4: three
 // rounds in flight with counted vmcnt waits, one workgroup per CU -- for grids of at most one workgroup per CU (the 4-step
@@ -63,10 +61,8 @@ __global__ __launch_bounds__(256) void uic_gemm_tn_kernel(const UicGemmTnParams 
     char* dB = dA + 16384;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcA[i] + (size_t)kt * strideA),
-                                       (__attribute__((address_space(3))) void*)(dA + i * 1024), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(srcB[i] + (size_t)kt * strideB),
-                                       (__attribute__((address_space(3))) void*)(dB + i * 1024), 16, 0, 0);
+      gemm::dma16(srcA[i] + (size_t)kt * strideA, dA + i * 1024);
+      gemm::dma16(srcB[i] + (size_t)kt * strideB, dB + i * 1024);
     }
   };
 
@@ -79,11 +75,7 @@ __global__ __launch_bounds__(256) void uic_gemm_tn_kernel(const UicGemmTnParams 
       for (int k = 0; k < 16; ++k) acc[i][j][k] = 0.f;
 
   int kt0 = 0, nt = p.K / 64;
-  if (p.splitk > 1) {
-    const int tps = (nt + p.splitk - 1) / p.splitk;
-    kt0 = blockIdx.z * tps;
-    nt = max(0, min(nt - kt0, tps));
-  }
+  gemm::splitk_slice(p.splitk, blockIdx.z, kt0, nt);
 
   // Transposed fragment reads.  16-lane group g of the wave: k half = g >> 1 (MFMA lanes 0-31 carry k 0..7, lanes 32-63
   // k 8..15 of a 16-k step), column block = g & 1 (columns 0-15 / 16-31 of the 32-wide operand tile).  Inside the group
@@ -121,7 +113,7 @@ __global__ __launch_bounds__(256) void uic_gemm_tn_kernel(const UicGemmTnParams 
   asm volatile("s_waitcnt lgkmcnt(" #N ")"                                                                         \
                : "+v"(S##a0l), "+v"(S##a0h), "+v"(S##a1l), "+v"(S##a1h), "+v"(S##b0l), "+v"(S##b0h), "+v"(S##b1l), "+v"(S##b1h)); \
   __builtin_amdgcn_sched_barrier(0)
-#define TN_OP(lo, hi) __builtin_bit_cast(bf16x8, (u32x4v){lo.x, lo.y, hi.x, hi.y})
+#define TN_OP(lo, hi) __builtin_bit_cast(bf16x8, (u32x4){lo.x, lo.y, hi.x, hi.y})
 #define TN_MFMA4(S)                                                                                                          \
   do {                                                                                                                       \
     acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(TN_OP(S##a0l, S##a0h), TN_OP(S##b0l, S##b0h), acc[0][0], 0, 0, 0);   \
@@ -213,19 +205,19 @@ __global__ __launch_bounds__(256) void uic_gemm_tn_kernel(const UicGemmTnParams 
         if (small && rows_ok && !p.accumulate) {
 #pragma unroll
           for (int reg = 0; reg < 16; ++reg)
-            C[(unsigned)(m0 + (wm * 2 + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half) * (unsigned)ldc + (unsigned)cc] = acc[i][j][reg];
+            C[(unsigned)(m0 + (wm * 2 + i) * 32 + gemm::c32_row(reg, half)) * (unsigned)ldc + (unsigned)cc] = acc[i][j][reg];
         } else if (small && rows_ok) {
           float old[16];
 #pragma unroll
           for (int reg = 0; reg < 16; ++reg)
-            old[reg] = C[(unsigned)(m0 + (wm * 2 + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half) * (unsigned)ldc + (unsigned)cc];
+            old[reg] = C[(unsigned)(m0 + (wm * 2 + i) * 32 + gemm::c32_row(reg, half)) * (unsigned)ldc + (unsigned)cc];
 #pragma unroll
           for (int reg = 0; reg < 16; ++reg)
-            C[(unsigned)(m0 + (wm * 2 + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half) * (unsigned)ldc + (unsigned)cc] = old[reg] + acc[i][j][reg];
+            C[(unsigned)(m0 + (wm * 2 + i) * 32 + gemm::c32_row(reg, half)) * (unsigned)ldc + (unsigned)cc] = old[reg] + acc[i][j][reg];
         } else {
 #pragma unroll
           for (int reg = 0; reg < 16; ++reg) {
-            const int row = m0 + (wm * 2 + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+            const int row = m0 + (wm * 2 + i) * 32 + gemm::c32_row(reg, half);
             if (row >= p.M) continue;
             float* o = C + (size_t)row * ldc + cc;
             *o = p.accumulate ? *o + acc[i][j][reg] : acc[i][j][reg];
@@ -234,13 +226,14 @@ __global__ __launch_bounds__(256) void uic_gemm_tn_kernel(const UicGemmTnParams 
       }
     return;
   }
+  // raw partial tile -> slab[z]  (the same text as in uic_gemm_glds_kernel, gemm_glds.hip: as one function it changed both kernels' branches)
   float* slab = p.slab + (size_t)blockIdx.z * p.M * p.N;
   if (m0 + 128 <= p.M && n0 + 128 <= p.N && (size_t)p.M * (size_t)p.N < ((size_t)1 << 31)) {   // whole tile: no tests, 32-bit offsets
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const unsigned ro = (unsigned)(m0 + (wm * 2 + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half) * (unsigned)p.N + (unsigned)(n0 + wn * 64 + r32);
+        const unsigned ro = (unsigned)(m0 + (wm * 2 + i) * 32 + gemm::c32_row(reg, half)) * (unsigned)p.N + (unsigned)(n0 + wn * 64 + r32);
         slab[ro] = acc[i][0][reg];
         slab[ro + 32] = acc[i][1][reg];
       }
@@ -254,98 +247,13 @@ __global__ __launch_bounds__(256) void uic_gemm_tn_kernel(const UicGemmTnParams 
       if (col >= p.N) continue;
 #pragma unroll
       for (int reg = 0; reg < 16; ++reg) {
-        const int row = m0 + (wm * 2 + i) * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * half;
+        const int row = m0 + (wm * 2 + i) * 32 + gemm::c32_row(reg, half);
         if (row < p.M) slab[(size_t)row * p.N + col] = acc[i][j][reg];
       }
     }
 }
 
-// blockIdx.y picks the destination (a uniform select: indexing an array of the by-value structs would put it in scratch)
-__global__ void splitk_reduce_multi_kernel(const float* __restrict__ slab, int splitk, int M, int N, UicSlabDest d0, UicSlabDest d1,
-                                           UicSlabDest d2, UicSlabDest d3, int accumulate) {
-  const int k = blockIdx.y;
-  float* const C = k == 0 ? d0.C : k == 1 ? d1.C : k == 2 ? d2.C : d3.C;
-  const int ldc = k == 0 ? d0.ldc : k == 1 ? d1.ldc : k == 2 ? d2.ldc : d3.ldc;
-  const int col0 = k == 0 ? d0.col0 : k == 1 ? d1.col0 : k == 2 ? d2.col0 : d3.col0;
-  const int ncols = k == 0 ? d0.ncols : k == 1 ? d1.ncols : k == 2 ? d2.ncols : d3.ncols;
-  const size_t stride = (size_t)gridDim.x * blockDim.x;
-  const size_t total = (size_t)M * ncols;
-  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
-    const int row = (int)(i / ncols), c = (int)(i - (size_t)row * ncols);
-    const float* src = slab + (size_t)row * N + col0 + c;
-    float v = 0.f;
-    for (int z = 0; z < splitk; ++z) v += src[(size_t)z * M * N];
-    float* o = C + (size_t)row * ldc + c;
-    *o = accumulate ? *o + v : v;
-  }
-}
-
-// the same, four columns per lane and the row from the grid (no division, 16-byte accesses): every extent and leading dimension
-// a multiple of 4 and 16-byte aligned pointers
-__global__ void splitk_reduce_multi_vec_kernel(const float* __restrict__ slab, int splitk, int M, int N, UicSlabDest d0, UicSlabDest d1,
-                                               UicSlabDest d2, UicSlabDest d3, int accumulate) {
-  const int k = blockIdx.y;
-  float* const C = k == 0 ? d0.C : k == 1 ? d1.C : k == 2 ? d2.C : d3.C;
-  const int ldc = k == 0 ? d0.ldc : k == 1 ? d1.ldc : k == 2 ? d2.ldc : d3.ldc;
-  const int col0 = k == 0 ? d0.col0 : k == 1 ? d1.col0 : k == 2 ? d2.col0 : d3.col0;
-  const int ncols = k == 0 ? d0.ncols : k == 1 ? d1.ncols : k == 2 ? d2.ncols : d3.ncols;
-  const size_t MN = (size_t)M * N;
-  if (ncols % 4 || col0 % 4 || ldc % 4 || ((size_t)C & 15)) {      // a destination that cannot take 16-byte accesses (a bias column): one column per lane
-    const int c1 = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c1 >= ncols) return;
-    for (int row = blockIdx.z; row < M; row += gridDim.z) {
-      const float* src = slab + (size_t)row * N + col0 + c1;
-      float v = 0.f;
-      for (int z = 0; z < splitk; ++z) v += src[(size_t)z * MN];
-      float* o = C + (size_t)row * ldc + c1;
-      *o = accumulate ? *o + v : v;
-    }
-    return;
-  }
-  const int c = (blockIdx.x * blockDim.x + threadIdx.x) * 4;
-  if (c >= ncols) return;
-  for (int row = blockIdx.z; row < M; row += gridDim.z) {
-    const float* src = slab + (size_t)row * N + col0 + c;
-    float4 v = *(const float4*)src;
-    for (int z = 1; z < splitk; ++z) {
-      const float4 w = *(const float4*)(src + (size_t)z * MN);
-      v.x += w.x; v.y += w.y; v.z += w.z; v.w += w.w;
-    }
-    float4* o = (float4*)(C + (size_t)row * ldc + c);
-    if (accumulate) { const float4 w = *o; v.x = w.x + v.x; v.y = w.y + v.y; v.z = w.z + v.z; v.w = w.w + v.w; }
-    *o = v;
-  }
-}
-
 }  // namespace
-
-int uic_splitk_reduce_multi_launch(const float* slab, int splitk, int M, int N, const UicSlabDest* dst, int nd, int accumulate, hipStream_t s) {
-  UIC_REQUIRE(nd >= 1 && nd <= 4, "splitk_reduce_multi: %d destinations", nd);
-  UicSlabDest d[4] = {dst[0], dst[nd > 1 ? 1 : 0], dst[nd > 2 ? 2 : 0], dst[nd > 3 ? 3 : 0]};
-  size_t cols = 0;
-  for (int i = 0; i < nd; ++i) cols += dst[i].ncols;
-  const bool vec = N % 4 == 0 && ((uintptr_t)slab & 15) == 0 && ((size_t)M * N) % 4 == 0;
-  int maxt = 0;      // lanes a destination needs along its columns: ncols / 4, or ncols where it takes the one-column path
-  for (int i = 0; i < nd; ++i) {
-    const bool v4 = dst[i].ncols % 4 == 0 && dst[i].col0 % 4 == 0 && dst[i].ldc % 4 == 0 && ((uintptr_t)dst[i].C & 15) == 0;
-    const int t = v4 ? dst[i].ncols / 4 : dst[i].ncols;
-    maxt = t > maxt ? t : maxt;
-  }
-  if (vec && M > 0 && maxt > 0) {
-    const int bt = maxt >= 256 ? 256 : ((maxt + 63) / 64) * 64;
-    const unsigned gz = (unsigned)(M > 65535 ? 65535 : M);
-    hipLaunchKernelGGL(splitk_reduce_multi_vec_kernel, dim3((unsigned)((maxt + bt - 1) / bt), (unsigned)nd, gz), dim3(bt), 0, s, slab, splitk, M, N,
-                       d[0], d[1], d[2], d[3], accumulate);
-    UIC_LAUNCH_CHECK("splitk_reduce_multi_vec");
-    return UIC_OK;
-  }
-  size_t g = ((size_t)M * cols / nd + 255) / 256;
-  if (g > 2048) g = 2048;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL(splitk_reduce_multi_kernel, dim3((unsigned)g, (unsigned)nd), dim3(256), 0, s, slab, splitk, M, N, d[0], d[1], d[2], d[3], accumulate);
-  UIC_LAUNCH_CHECK("splitk_reduce_multi");
-  return UIC_OK;
-}
 
 bool uic_gemm_tn_eligible(const UicGemmTnParams& p) {
   // (M need not be a multiple of 8: lda is, so the last 16-byte chunk of a k-row reads padding columns inside the row -- whatever

@@ -37,13 +37,12 @@
 // B may be up to 4 column segments living in different matrices (multiples of 128 columns: every unit lies in ONE segment); the
 // epilogue writes (or adds to) up to 4 destinations directly, or stores raw f32 partial tiles into slab[z][M][N] for the
 // deterministic split-K reduction (uic_splitk_reduce_multi_launch).
-#include "uic_common.h"
-#include <type_traits>
+#include "gemm_internal.h"
 
 namespace {
 
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2t;
-typedef __attribute__((ext_vector_type(4))) unsigned u32x4t;
+using gemm::u32x4;
 
 #define TP_RD(dst, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off))
 
@@ -60,19 +59,12 @@ __global__ __launch_bounds__(512) void uic_gemm_tnpp_kernel(const UicGemmTnParam
   {
     const int gx = gridDim.x, gy = gridDim.y, nblk = gx * gy;
     const int lin = blockIdx.x + gx * blockIdx.y;
-    const int q = nblk >> 3, r = nblk & 7, xcd = lin & 7, idx = lin >> 3;
-    const int lp = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    constexpr int GM = 8;
-    const int width = GM * gy;
-    const int first = (lp / width) * GM;
-    const int gsz = min(gx - first, GM);
-    const int rem = lp % width;
-    bm = first + rem % gsz;
-    bn = rem / gsz;
+    gemm::grouped_tile(gemm::xcd_run(lin, nblk), gx, gy, bm, bn);
   }
   const int m0 = bm * 256, n0 = bn * 256;
 
-  // K tiles of this workgroup: all of them, or slice blockIdx.z of a split-K launch (an even number each; the launcher checks)
+  // K tiles of this workgroup: all of them, or slice blockIdx.z of a split-K launch (an even number each; the launcher checks).
+  // Written out as in uic_gemm_pp_kernel, whose instruction streams a shared function for this exact-division form changed.
   int kt0 = 0, nt = p.K / 64;
   if (p.splitk > 1) {
     const int tps = nt / p.splitk;
@@ -110,9 +102,7 @@ __global__ __launch_bounds__(512) void uic_gemm_tnpp_kernel(const UicGemmTnParam
     }
   }
   const unsigned dst0 = (unsigned)(wave * 2048);    // this wave's first instruction inside a unit; the second is 1 KB up
-#define TP_GLDS(BASE, OFF, DST)                                                                                           \
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)((BASE) + (size_t)(OFF)),              \
-                                   (__attribute__((address_space(3))) void*)(smem + (DST)), 16, 0, 0)
+#define TP_GLDS(BASE, OFF, DST) gemm::dma16((BASE) + (size_t)(OFF), smem + (DST))
 #define TP_STAGE_A(S, BUF)                                                                                   \
   do {                                                                                                      \
     TP_GLDS(baseA[S], offA[S][0], (BUF) * 65536u + (S) * 16384u + dst0);                                    \
@@ -214,7 +204,7 @@ __global__ __launch_bounds__(512) void uic_gemm_tnpp_kernel(const UicGemmTnParam
     TP_TIE_A; TP_TIE_B(BX);                                \
     __builtin_amdgcn_sched_barrier(0);                     \
   } while (0)
-#define TP_OP(X) __builtin_bit_cast(bf16x8, (u32x4t){X[0].x, X[0].y, X[1].x, X[1].y})
+#define TP_OP(X) __builtin_bit_cast(bf16x8, (u32x4){X[0].x, X[0].y, X[1].x, X[1].y})
 #define TP_MFMA(RT0, CT, BX)                                                                                                    \
   do {                                                                                                                          \
     __builtin_amdgcn_s_setprio(1);                                                                                              \
