@@ -574,6 +574,37 @@ size_t uic_nmt_translate_workspace_bytes(const uic_nmt_dims* d, int32_t beam_siz
 int uic_nmt_translate(const uic_nmt_dims* d, const uic_nmt_weights* w, const int64_t* src, int32_t beam_size, int32_t max_steps,
                       void* workspace, int64_t* hyp_out, float* score_out, float* attn_out, int32_t* n_iter_out, void* stream);
 
+/* ---- the pivot bridge (csrc/pivot.hip): the glue of eval_split_coco_unpaired (P/eval_utils.py:329-473) on token ids, between
+ * the captioner's rows, uic_nmt_translate and the uic_langeval_* scorers.  The word <-> id work is three int32 tables built once
+ * on the host (misc/pivot.py).  onmt.Constants: PAD 0, UNK 1, BOS 2, EOS 3.  Both entries only enqueue; a bad argument returns
+ * non-zero with uic_last_error_string naming it, launches nothing and touches no output; B == 0 is a successful no-op.  Integer
+ * and gather work: the same bits on every call.
+ *
+ * uic_pivot_source: caption rows -> the translator's source batch (decode_sequence + split + Dict.convertToIdx(words, UNK_WORD),
+ * O/Dict.py:116-132, + the padding of onmt.Dataset).  seq [B, ld_seq >= L] int64, the first L columns are the decode steps;
+ * table [V1] int32: caption id -> source-dictionary id.  A token <= 0 ends the caption (0 = end, -1 = a timed-out decode); a
+ * token >= V1 maps to UNK.  src [L, B] int64 time-major: table[seq[b, t]] before the end, PAD behind it; lengths [B] int32;
+ * max_len [1] int32 = the largest length.  The caller reads max_len back once and passes src[:max_len] on: the reference pads a
+ * batch to its longest sentence and translateBatch ENCODES the padding (the encoder runs without lengths there), so the padded
+ * width is part of the result.  An empty caption becomes the one-token sentence [UNK], length 1 (the reference crashes on an
+ * empty source line).  No sort by length: onmt.Dataset sorts only for packing, translateBatch does not pack, and a sentence's
+ * result depends on the padded width and not on the order of the batch. */
+int uic_pivot_source(const int64_t* seq, int32_t ld_seq, int32_t B, int32_t L, const int32_t* table, int32_t V1, int64_t* src,
+                     int32_t* lengths, int32_t* max_len, void* stream);
+/* uic_pivot_target: NMTModel.buildTargetTokens (P/models/NMT_Models.py:312-320) on ids.  hyp [B, ld_hyp] int64 and
+ * attn [B, attn_ld, S] f32 as uic_nmt_translate leaves them, the first n_steps columns / rows valid; src_len [B] int32 (the
+ * lengths of uic_pivot_source); seq [B, ld_seq] the captioner's rows; tgt_table [Vt] int32: target-dictionary id -> scoring id;
+ * copy_table [V1] int32: caption id -> scoring id.  Per sentence: with m the first column holding EOS, the tokens are
+ * hyp[b, :m]; without an EOS among the n_steps columns they are hyp[b, :n_steps - 1] (convertToLabels(...)[:-1] drops the last
+ * label whether or not it is EOS), cut at L_out.  A token UNK is replaced by the pivot word the decoder looked at:
+ * j = arg-max of attn[b, i, :src_len[b]] (lowest index on ties), out = copy_table[seq[b, j]] (a seq token outside [0, V1) reads
+ * copy_table[0]) and repl = j.  Any other token: out = tgt_table[tok], repl = -1; a token outside [0, Vt) is UNK without
+ * replacement, out = tgt_table[1].  out [B, L_out] int64 (0 behind the tokens), out_len [B] int32, repl [B, L_out] int32 (-1
+ * behind the tokens). */
+int uic_pivot_target(const int64_t* hyp, int32_t ld_hyp, int32_t n_steps, const float* attn, int32_t attn_ld, int32_t S,
+                     const int32_t* src_len, const int64_t* seq, int32_t ld_seq, int32_t B, const int32_t* tgt_table, int32_t Vt,
+                     const int32_t* copy_table, int32_t V1, int32_t L_out, int64_t* out, int32_t* out_len, int32_t* repl, void* stream);
+
 /* ---- data-parallel gradient exchange on RCCL (replaces DataParallel's reduce-add, P/trainer.py:74,88-89), for callers
  * that do not use torch.distributed.  librccl is dlopen()ed on first use.  uic_comm_unique_id: rank 0 obtains the 128-byte
  * rendezvous id and hands it to every rank out of band (file, socket, MPI, a torch store); uic_comm_init: collective over all

@@ -11,7 +11,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
-SOURCES = ["api.hip", "gemm.hip", "gemm_skinny.hip", "gemm_glds.hip", "gemm_pp.hip", "gemm_tn.hip", "gemm_tn_pp.hip", "splitk_reduce.hip", "attention.hip", "rnn_persist.hip", "rnn_persist_generic.hip", "rnn_persist_ws.hip", "rnn_bwd_persist.hip", "bptt_fused.hip", "pointwise.hip", "embedding.hip", "lstm_cell.hip", "adam.hip", "sampling.hip", "live_rows.hip", "criterion.hip", "batchnorm.hip", "beam.hip", "ensemble.hip", "wgrad.hip", "topdown_layout.hip", "topdown_features.hip", "topdown_step.hip", "topdown_train.hip", "topdown_decode.hip", "fcmodel.hip", "nmt_kernels.hip", "nmt_layout.hip", "nmt_train.hip", "nmt_translate.hip", "nmt_persist.hip", "cider.hip", "loader.hip", "loader_io.hip", "comm.hip", "discriminator.hip", "gcn.hip", "transformer.hip", "adaatt.hip"]
+SOURCES = ["api.hip", "gemm.hip", "gemm_skinny.hip", "gemm_glds.hip", "gemm_pp.hip", "gemm_tn.hip", "gemm_tn_pp.hip", "splitk_reduce.hip", "attention.hip", "rnn_persist.hip", "rnn_persist_generic.hip", "rnn_persist_ws.hip", "rnn_bwd_persist.hip", "bptt_fused.hip", "pointwise.hip", "embedding.hip", "lstm_cell.hip", "adam.hip", "sampling.hip", "live_rows.hip", "criterion.hip", "batchnorm.hip", "beam.hip", "ensemble.hip", "wgrad.hip", "topdown_layout.hip", "topdown_features.hip", "topdown_step.hip", "topdown_train.hip", "topdown_decode.hip", "fcmodel.hip", "nmt_kernels.hip", "nmt_layout.hip", "nmt_train.hip", "nmt_translate.hip", "pivot.hip", "nmt_persist.hip", "cider.hip", "loader.hip", "loader_io.hip", "comm.hip", "discriminator.hip", "gcn.hip", "transformer.hip", "adaatt.hip"]
 LIB = os.path.join(HERE, "libuic_hip.so")
 
 

@@ -16,6 +16,10 @@ gradients of every parameter (generator included).  Options outside the referenc
 path (GRU cells, unidirectional encoder, coverage/fertility/copy attention, context gates, positional encodings,
 a carried decoder state) raise NotImplementedError.
 
+Translation: `translate_device` runs the beam search and leaves hypotheses, scores and attention on the device (what the
+unpaired validation chain consumes, misc/pivot.py); `translateBatch` is the reference's list-shaped surface on top of it, and
+`translate` the reference's word-list surface (words -> ids on the host, ids -> words through uic_pivot_target, csrc/pivot.hip).
+
 There is no eager fallback: the nn.LSTM / nn.LSTMCell / nn.Linear modules below are parameter containers that give the
 reference's state_dict keys and initialisation; they are never called.
 """
@@ -306,14 +310,13 @@ class NMTModel(nn.Module):
         return {k: sd[k] for k in self.param_names}
 
     # ---- reference surface
-    def translateBatch(self, batch, beam_size=15, max_steps=100):
-        """NMTModel.translateBatch (P/models/NMT_Models.py:322-395): beam-search translation of `batch.src` [S, B, 1] with
-        the reference's hard-coded beam 15 / 100 steps.  Returns (allHyp, allScores, allAttn, goldScores) shaped like the
-        reference's: per sentence a 1-best list of token-id lists (as long as the number of decoder steps taken -- cut
-        them at EOS like buildTargetTokens does), its score, and its attention [steps, valid source positions]."""
+    def translate_device(self, src, beam_size=15, max_steps=100):
+        """What translateBatch computes, left on the device: src [S, B] (or [S, B, 1]) int64 -> (hyp [B, max_steps] int64,
+        scores [B] f32, attn [B, max_steps, S] f32 with the PAD source columns dropped and the rest packed to the left, n_iter):
+        the first n_iter columns of hyp / rows of attn are valid (include/uic_hip.h, uic_nmt_translate).  The only host waits
+        are the translator's own stop checks."""
         if self.training:
             raise NotImplementedError("translateBatch runs in eval mode")
-        src = batch.src
         if src.dim() == 3:
             src = src[:, :, 0]
         src = src.contiguous()
@@ -332,12 +335,62 @@ class NMTModel(nn.Module):
             w = eng.weights({k: v.detach() for k, v in self._param_dict().items()})
             check(eng.lib.uic_nmt_translate(C.byref(d), C.byref(w), ptr(src), beam_size, max_steps, ptr(ws), ptr(hyp), ptr(scores),
                                             ptr(attn), C.byref(n_iter), stream()), "nmt_translate")
-        n = n_iter.value
+        return hyp, scores, attn, n_iter.value
+
+    def translateBatch(self, batch, beam_size=15, max_steps=100):
+        """NMTModel.translateBatch (P/models/NMT_Models.py:322-395): beam-search translation of `batch.src` [S, B, 1] with
+        the reference's hard-coded beam 15 / 100 steps.  Returns (allHyp, allScores, allAttn, goldScores) shaped like the
+        reference's: per sentence a 1-best list of token-id lists (as long as the number of decoder steps taken -- cut
+        them at EOS like buildTargetTokens does), its score, and its attention [steps, valid source positions]."""
+        src = batch.src
+        if src.dim() == 3:
+            src = src[:, :, 0]
+        hyp, scores, attn, n = self.translate_device(src, beam_size, max_steps)
+        B = src.shape[1]
         hyp_h, valid = hyp[:, :n].cpu(), (src != PAD).sum(0).cpu()
         allHyp = [[[int(t) for t in hyp_h[b]]] for b in range(B)]
         allScores = [scores[b:b + 1] for b in range(B)]
         allAttn = [[attn[b, :n, :int(valid[b])]] for b in range(B)]
         return allHyp, allScores, allAttn, scores.new_zeros(B)
+
+    def translate(self, srcBatch, beam_size=15, max_steps=100):
+        """NMTModel.translate (P/models/NMT_Models.py:297-320, 397-412): lists of source words -> per sentence a one-best list of
+        target word lists.  Words -> ids is src_dict.convertToIdx(words, UNK_WORD) (no BOS / EOS on the source side); all
+        sentences form ONE batch, padded to the longest, in the caller's order (the reference's onmt.Dataset sorts by length for
+        packing only and translateBatch does not pack, so the order does not change a sentence's result).  ids -> words is
+        buildTargetTokens on the device (uic_pivot_target): the tokens before EOS -- or all but the last without one -- and at an
+        UNK the caller's own source word the decoder attended to most."""
+        from ..misc import pivot
+        if not all(hasattr(d, 'labelToIdx') or hasattr(d, 'items') for d in (self.src_dict, self.tgt_dict)):
+            raise RuntimeError("NMTModel.translate needs word dictionaries: construct the model with src_dict / tgt_dict objects "
+                               "(onmt.Dict-like, or word -> id mappings), not with vocabulary sizes")
+        sd, td = pivot.as_dict(self.src_dict), pivot.as_dict(self.tgt_dict)
+        B = len(srcBatch)
+        if B == 0:
+            return []
+        if any(len(words) == 0 for words in srcBatch):
+            raise ValueError("NMTModel.translate: an empty source sentence (the reference's readSrcLine fails on one too)")
+        S = max(len(words) for words in srcBatch)
+        src_h = np.zeros((S, B), dtype=np.int64)
+        for b, words in enumerate(srcBatch):
+            src_h[:len(words), b] = [sd.lookup(w, pivot.UNK) for w in words]
+        dev = self.engine.device()
+        src = torch.from_numpy(src_h).to(dev)
+        src_len = torch.tensor([len(words) for words in srcBatch], dtype=torch.int32, device=dev)
+        hyp, scores, attn, n = self.translate_device(src, beam_size, max_steps)
+        Vt = self.decoder.embeddings.word_lut.num_embeddings
+        ident = torch.arange(Vt, dtype=torch.int32, device=dev)
+        zero_rows = torch.zeros(B, S, dtype=torch.int64, device=dev)
+        out = torch.empty(B, n, dtype=torch.int64, device=dev)
+        out_len = torch.empty(B, dtype=torch.int32, device=dev)
+        repl = torch.empty(B, n, dtype=torch.int32, device=dev)
+        check(self.engine.lib.uic_pivot_target(ptr(hyp), hyp.shape[1], n, ptr(attn), attn.shape[1], S, ptr(src_len), ptr(zero_rows), S, B,
+                                               ptr(ident), Vt, ptr(ident), 1, n, ptr(out), ptr(out_len), ptr(repl), stream()), "pivot_target")
+        out_h, len_h, repl_h = out.cpu().tolist(), out_len.cpu().tolist(), repl.cpu().tolist()
+        predBatch = []
+        for b in range(B):
+            predBatch.append([[srcBatch[b][repl_h[b][i]] if repl_h[b][i] >= 0 else td.label(out_h[b][i]) for i in range(len_h[b])]])
+        return predBatch
 
     def forward(self, src, tgt, lengths, dec_state=None):
         """src [S,B,1] int64, tgt [T,B] int64, lengths [1,B] (sorted descending).  Returns (outputs [T-1,B,H],

@@ -889,6 +889,39 @@ class Trainer(object):
                 self.best_i2t_val_score = current_score
                 self.best_flag_i2t = True
 
+    def build_pivot(self, caption_vocab, scoring_vocab, src_dict=None, tgt_dict=None, max_words=None):
+        """The bridge of the unpaired validation pass (misc/pivot.py): `caption_vocab` / `scoring_vocab` are the ix_to_word of the
+        pivot-language loader and of the COCO loader; the dictionaries default to the NMT model's.  Stored as self.pivot_bridge."""
+        from .misc import pivot
+        src_dict = self.nmt_model.src_dict if src_dict is None else src_dict
+        tgt_dict = self.nmt_model.tgt_dict if tgt_dict is None else tgt_dict
+        device = next(self.nmt_model.parameters()).device
+        self.pivot_bridge = pivot.PivotBridge(caption_vocab, src_dict, tgt_dict, scoring_vocab, device=device,
+                                              max_words=pivot.MAX_WORDS if max_words is None else max_words)
+        return self.pivot_bridge
+
+    def eval_unpaired(self, loader, coco_loader):
+        """Trainer.eval with opt.coco_eval_flag (P/trainer.py:195-215): eval_utils.eval_split_coco_unpaired over the 'val' splits of
+        the pivot-language `loader` and of `coco_loader`.  Sets i2t_val_loss, predictions, coco_predictions, lang_stats,
+        coco_lang_stats, best_i2t_val_score and best_flag_i2t: a strict `>` on coco_lang_stats['CIDEr'] (opt.language_eval == 1)
+        or on -val_loss.  Needs build_nmt and build_pivot; the models' train / eval modes are restored."""
+        from . import eval_utils
+        if self.exchange.world_size > 1:
+            raise NotImplementedError("Trainer.eval_unpaired on %d ranks: a sharded validation pass needs collectives for the captions "
+                                      "and the losses; evaluate on one rank" % self.exchange.world_size)
+        if getattr(self, 'pivot_bridge', None) is None:
+            raise RuntimeError("Trainer.eval_unpaired needs Trainer.build_pivot(caption_vocab, scoring_vocab) first")
+        self.predictions, self.coco_predictions = [], []
+        eval_kwargs = {'split': 'val', 'dataset': getattr(self.opt, 'input_json', '')}
+        eval_kwargs.update(vars(self.opt))
+        eval_kwargs['pivot_bridge'] = self.pivot_bridge
+        eval_tmp = eval_utils.eval_split_coco_unpaired(self.opt, loader, coco_loader, self.dp_i2t_model, self.dp_nmt_model, eval_kwargs)
+        self.i2t_val_loss, self.predictions, self.coco_predictions, self.lang_stats, self.coco_lang_stats, _, _ = eval_tmp
+        current_score = self.coco_lang_stats['CIDEr'] if getattr(self.opt, 'language_eval', 0) == 1 else - self.i2t_val_loss
+        if self.best_i2t_val_score is None or current_score > self.best_i2t_val_score:
+            self.best_i2t_val_score = current_score
+            self.best_flag_i2t = True
+
     def eval_nmt(self, batches):
         """The NMT half of the validation pass (P/trainer.py:212-215, P/eval_utils.py:313-317): the given validation batches
         through dp_nmt_model in eval mode and a fresh NMT_loss, no backward pass.  Sets nmt_valid_ppl, nmt_valid_acc,
