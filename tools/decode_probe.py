@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Persistent decode launch (rnn_persist.hip, decode mode) against the per-step launch chain at BASELINE configs[1] size:
 agreement of tokens / log-probs (greedy, multinomial, forced replay), pass times, phase stamps of the decode tail.
-    python tools/decode_probe.py [--dbg] [--iters 20]"""
+    python tools/decode_probe.py [--dbg] [--iters 20]
+With --beam B: only the time of one beam search (mode='sample', beam_size B) of --model at that size, for A/B runs of the host-side
+decode drivers (UIC_LIB).
+    python tools/decode_probe.py --model transformer --beam 3 --rows 32"""
 import argparse
 import os
 import sys
@@ -12,6 +15,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--iters", type=int, default=20)
 ap.add_argument("--dbg", action="store_true")
 ap.add_argument("--rows", type=int, default=0, help="images (default: the bench config's 128)")
+ap.add_argument("--model", default="topdown", choices=["topdown", "transformer", "adaatt"])
+ap.add_argument("--beam", type=int, default=0, help="time a beam search of this many beams and stop")
 args = ap.parse_args()
 
 import torch
@@ -22,14 +27,20 @@ from unpaired_image_captioning_amd.synthetic import synthetic_batch
 
 c = CFG
 n_img = args.rows or c["n_img"]
-model = models.setup(make_opt("bf16", 1234)).cuda()
+opt = make_opt("bf16", 1234)
+if args.model == "transformer":      # opts.py's defaults: 6 layers, d_model = input_encoding_size, d_ff = rnn_size
+    opt.caption_model, opt.num_layers, opt.rnn_size, opt.i2t_train_flag = "transformer", 6, 2048, 0
+elif args.model == "adaatt":
+    opt.caption_model, opt.i2t_train_flag = "adaatt", 0
+model = models.setup(opt).cuda()
 # a logit layer with some contrast, or every row decodes the same flat distribution
-with torch.no_grad():
-    lw = model.logit.weight if isinstance(model.logit, torch.nn.Linear) else model.logit[-1].weight
-    lw.mul_(25.0)
+if args.model != "transformer":
+    with torch.no_grad():
+        lw = model.logit.weight if isinstance(model.logit, torch.nn.Linear) else model.logit[-1].weight
+        lw.mul_(25.0)
 batch = {k: v.cuda() for k, v in synthetic_batch(n_img, c["S"], c["R"], c["D"], c["V"], c["L"], seed=1).items()}
 fc, att, am = batch["fc_feats"], batch["att_feats"], batch.get("att_masks")
-eng = model.engine
+eng = getattr(model, "engine", None)
 Lsteps = c["L"]
 
 
@@ -54,6 +65,16 @@ def timeit(fn, iters):
     torch.cuda.synchronize()
     return a.elapsed_time(b) / iters
 
+
+if args.beam:
+    model.eval()
+    search = lambda: model(fc, None, att, am, opt={"beam_size": args.beam}, mode="sample")
+    seq, _ = search()
+    print("%s beam %d: %.3f ms   (%d images x %d steps, mean length %.2f)" % (args.model, args.beam, timeit(search, args.iters), seq.shape[0],
+                                                                             Lsteps, (seq > 0).sum(1).float().mean().item()))
+    sys.exit(0)
+if args.model != "topdown":
+    sys.exit("the persistent decode launch is the TopDown captioner's; give --beam")
 
 st0 = L.persistent_status()
 for name, sm, tr, keep in (("greedy, eval", 1, False, False), ("multinomial, eval", 0, False, False),

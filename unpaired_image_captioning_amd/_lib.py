@@ -209,6 +209,16 @@ def mha_lds_bytes(Sk, d_k):
 
 
 BEAM_MAX = 16              # UIC_BEAM_MAX
+
+
+def done_list_buffers(n_img, L, B, device):
+    """Zeroed outputs of a `*_beam_done_lists` export after an L-step search with B beams: (count [n_img] int32, p [n_img, L*B],
+    seq [n_img, L*B, L] int64, logps likewise).  An image finishes at most B beams per step; behind its first count[k] entries the export
+    leaves zeros (a search clears its lists when it starts)."""
+    cnt = torch.zeros(n_img, dtype=torch.int32, device=device)
+    dp = torch.zeros(n_img, L * B, dtype=torch.float32, device=device)
+    dseq = torch.zeros((n_img, L * B, L), dtype=torch.int64, device=device)
+    return cnt, dp, dseq, torch.zeros_like(dseq, dtype=torch.float32)
 ADAATT_MAX_LAYERS = 2      # UIC_ADAATT_MAX_LAYERS
 LDS_BYTES = 160 * 1024     # per workgroup on gfx950
 

@@ -9,13 +9,15 @@
 //                            sentinel), softmax, the mask rule cat([m[:, :1], m]), PI . [fr ; att] + h_out_linear.  One workgroup
 //                            owns a row: no atomics, one fixed order of operations.
 // Everything else is the project's GEMM (every nn.Linear), its BatchNorm operators (att_embed), embedding.hip, sampling.hip and
-// beam.hip.  input_encoding_size == rnn_size == att_hid_size == H (the reference's view / cat need it, :385-386).
+// beam.hip -- the last two through decode_internal.h, which owns their buffers, the start of a pass and the beam loop; the beam
+// driver here supplies the step and gathers the (h, c) stacks by the surviving parents.  input_encoding_size == rnn_size == att_hid_size == H (the reference's view / cat need it, :385-386).
 //
 // Per decode step: embedding; ONE GEMM [xt | h_prev] x [w2h ; r_w2h | h2h ; r_h2h]^T (+ the per-row img_fc projection and the
 // summed biases, made once per call) -> [rows, (4 + maxout + 1) H]; the cell; fr_linear, fr_embed, ho_linear, ho_embed; the
 // attention; tanh(att2h); the logit layer(s).  The beams of an image share its p_att / att (row_div).
 #include "uic_common.h"
 #include "uic_host.h"
+#include "decode_internal.h"
 #include "../../include/uic_hip.h"
 #include <math.h>
 #include <string.h>
@@ -286,9 +288,8 @@ struct Layout {
   void* xt; float* sums; void* h[2][UIC_ADAATT_MAX_LAYERS]; float* c[2][UIC_ADAATT_MAX_LAYERS];
   void* fake; void* fr; void* hl; float* fr_e; float* hl_e; float* PI; void* aout; void* ah; void* lh[UIC_MAX_LOGIT_LAYERS - 1];
   float* logits;                      // [max(rows, (S - 1) N), V1p]
-  int64_t* it; int* unf; int* nunf;
-  float* bm_cand_val; int* bm_cand_idx; int64_t* bm_seq[2]; float* bm_lp[2]; float* bm_sum; int* bm_parent;
-  int* bm_done_count; float* bm_done_p; int64_t* bm_done_seq; float* bm_done_lp;
+  SampleScratch smp;                  // rows = N beam, step capacity S
+  BeamScratch beam;                   // the same rows, a done_count entry per image, step capacity S
   size_t total;
 };
 
@@ -348,21 +349,8 @@ Layout make_layout(const uic_adaatt_dims& d, const uic_adaatt_weights* w, void* 
   for (int l = 0; l + 1 < d.logit_layers; ++l) L.lh[l] = b.take(rows * H * Sz);
   const size_t lrows = rows > (S - 1) * N ? rows : (S - 1) * N;
   L.logits = (float*)b.take(lrows * V1p * 4);
-  L.it = (int64_t*)b.take(rows * 8);
-  L.unf = (int*)b.take(rows * 4);
-  L.nunf = (int*)b.take((S + 2) * UIC_NUNF_STRIPES * 4);
-  L.bm_cand_val = (float*)b.take(rows * UIC_BEAM_MAX * 4);
-  L.bm_cand_idx = (int*)b.take(rows * UIC_BEAM_MAX * 4);
-  for (int i = 0; i < 2; ++i) {
-    L.bm_seq[i] = (int64_t*)b.take(rows * S * 8);
-    L.bm_lp[i] = (float*)b.take(rows * S * 4);
-  }
-  L.bm_sum = (float*)b.take(rows * 4);
-  L.bm_parent = (int*)b.take(rows * 4);
-  L.bm_done_count = (int*)b.take(N * 4);
-  L.bm_done_p = (float*)b.take(rows * S * 4);
-  L.bm_done_seq = (int64_t*)b.take(rows * S * S * 8);
-  L.bm_done_lp = (float*)b.take(rows * S * S * 4);
+  L.smp.carve(b, rows, S);
+  L.beam.carve(b, rows, N, S);
   L.total = (b.off + 255) & ~(size_t)255;
   return L;
 }
@@ -665,20 +653,11 @@ int uic_adaatt_sample(const uic_adaatt_dims* d, const uic_adaatt_weights* w, con
   UIC_TRY(m.refresh());
   UIC_TRY(m.prepare(fc_feats, att_feats, att_masks));
   UIC_TRY(m.state_zero(N));
-  UIC_TRY(uic_fill_launch(L.it, 0, (size_t)N * 8, s));                // <bos> = 0 (AttModel.py:214-216)
-  UIC_TRY(uic_fill_launch(L.unf, 0, (size_t)N * 4, s));
-  UIC_TRY(uic_fill_launch(L.nunf, 0, (size_t)(d->S + 2) * UIC_NUNF_STRIPES * 4, s));
-  UIC_TRY(uic_fill_launch(seq, 0, (size_t)N * Lsteps * 8, s));
-  UIC_TRY(uic_fill_launch(seq_logp, 0, (size_t)N * Lsteps * 4, s));
+  UIC_TRY(sample_begin(L.smp, N, d->S, seq, seq_logp, (size_t)N * Lsteps, s));   // <bos> = 0 (AttModel.py:214-216)
   for (int t = 0; t < Lsteps; ++t) {
-    UIC_TRY(m.step(N, 1, L.it, 1, att_masks, t & 1, (t & 1) ^ 1, L.logits));
-    UicSampleParams p;
-    memset(&p, 0, sizeof(p));
-    p.dtype = m.dt; p.N = N; p.V1 = d->V1; p.ldv = m.V1p; p.t = t; p.L = Lsteps;
-    p.logits = L.logits; p.sample_max = sample_max; p.temperature = temperature; p.seed = seed;
-    p.decoding_constraint = decoding_constraint;
-    p.seq = seq; p.seq_logp = seq_logp; p.it = L.it; p.unfinished = L.unf; p.n_unfinished = L.nunf;
-    UIC_TRY(uic_sample_step_launch(p, s));
+    UIC_TRY(m.step(N, 1, L.smp.it, 1, att_masks, t & 1, (t & 1) ^ 1, L.logits));
+    UIC_TRY(uic_sample_step_launch(sample_params(L.smp, m.dt, N, d->V1, t, Lsteps, L.logits, sample_max, temperature, decoding_constraint, seed, nullptr,
+                                                 seq, seq_logp), s));
   }
   return UIC_OK;
 }
@@ -698,33 +677,18 @@ int uic_adaatt_sample_beam(const uic_adaatt_dims* d, const uic_adaatt_weights* w
   UIC_TRY(m.refresh());
   UIC_TRY(m.prepare(fc_feats, att_feats, att_masks));
   UIC_TRY(m.state_zero(rows));
-  UIC_TRY(uic_fill_launch(L.it, 0, (size_t)rows * 8, s));              // <bos> on every beam (AttModel.py:187-188)
-  for (int i = 0; i < 2; ++i) {
-    UIC_TRY(uic_fill_launch(L.bm_seq[i], 0, (size_t)rows * S * 8, s));
-    UIC_TRY(uic_fill_launch(L.bm_lp[i], 0, (size_t)rows * S * 4, s));
-  }
-  UIC_TRY(uic_fill_launch(L.bm_sum, 0, (size_t)rows * 4, s));
-  UIC_TRY(uic_fill_launch(L.bm_done_count, 0, (size_t)N * 4, s));
+  UIC_TRY(uic_fill_launch(L.smp.it, 0, (size_t)rows * 8, s));          // <bos> on every beam (AttModel.py:187-188)
   UicBeamParams p;
-  memset(&p, 0, sizeof(p));
-  p.n_img = N; p.B = B; p.L = Lsteps; p.V1 = d->V1; p.ldv = m.V1p;
-  p.decoding_constraint = decoding_constraint; p.max_ppl = max_ppl;
-  p.logits = L.logits; p.cand_val = L.bm_cand_val; p.cand_idx = L.bm_cand_idx;
-  p.beam_seq_hist[0] = L.bm_seq[0]; p.beam_seq_hist[1] = L.bm_seq[1]; p.beam_lp_hist[0] = L.bm_lp[0]; p.beam_lp_hist[1] = L.bm_lp[1];
-  p.beam_sum = L.bm_sum; p.parent = L.bm_parent; p.it = L.it;
-  p.done_count = L.bm_done_count; p.done_p = L.bm_done_p; p.done_seq = L.bm_done_seq; p.done_lp = L.bm_done_lp;
-  UIC_TRY(m.step(rows, B, L.it, 1, att_masks, 0, 1, L.logits));       // logprobs after <bos> (AttModel.py:190)
+  UIC_TRY(beam_begin(L.beam, L.logits, m.V1p, L.smp.it, N, B, S, d->V1, Lsteps, decoding_constraint, max_ppl, p, s));
+  UIC_TRY(m.step(rows, B, L.smp.it, 1, att_masks, 0, 1, L.logits));       // logprobs after <bos> (AttModel.py:190)
   const bool two = d->layers > 1;
-  for (int t = 0; t < Lsteps; ++t) {
-    p.t = t;
-    UIC_TRY(uic_beam_step_launch(p, s));
-    if (t + 1 == Lsteps) break;                                        // (the reference's last get_logprobs_state is never used)
+  auto advance = [&](int) -> int {
     // the states follow the surviving parents (CaptionModel.py:90-92): slot 1 -> slot 0
-    UIC_TRY(uic_beam_gather_launch(m.dt, L.bm_parent, rows, B, H, L.h[1][0], L.h[0][0], two ? L.h[1][1] : nullptr, two ? L.h[0][1] : nullptr,
+    UIC_TRY(uic_beam_gather_launch(m.dt, p.parent, rows, B, H, L.h[1][0], L.h[0][0], two ? L.h[1][1] : nullptr, two ? L.h[0][1] : nullptr,
                                    L.c[1][0], L.c[0][0], two ? L.c[1][1] : nullptr, two ? L.c[0][1] : nullptr, s));
-    UIC_TRY(m.step(rows, B, L.it, 1, att_masks, 0, 1, L.logits));
-  }
-  return uic_beam_final_launch(p, seq, seq_logp, s);
+    return m.step(rows, B, L.smp.it, 1, att_masks, 0, 1, L.logits);
+  };
+  return beam_search(p, Lsteps, advance, s, seq, seq_logp);
 }
 
 int uic_adaatt_beam_done_lists(const uic_adaatt_dims* d, void* workspace, int32_t Lsteps, int32_t beam_size, int32_t* done_count,
@@ -734,11 +698,7 @@ int uic_adaatt_beam_done_lists(const uic_adaatt_dims* d, void* workspace, int32_
   UIC_REQUIRE(beam_size >= 1 && beam_size == d->beam && Lsteps >= 1 && Lsteps <= d->S, "adaatt_beam_done_lists: bad sizes");
   hipStream_t s = (hipStream_t)stream;
   const Layout L = make_layout(*d, nullptr, workspace);
-  const size_t n_img = (size_t)d->N, LB = (size_t)Lsteps * beam_size;
-  UIC_TRY(uic_copy_launch(done_count, L.bm_done_count, n_img * 4, s));
-  UIC_TRY(uic_copy_launch(done_p, L.bm_done_p, n_img * LB * 4, s));
-  UIC_TRY(uic_copy_launch(done_seq, L.bm_done_seq, n_img * LB * Lsteps * 8, s));
-  return uic_copy_launch(done_lp, L.bm_done_lp, n_img * LB * Lsteps * 4, s);
+  return beam_done_lists(L.beam, d->N, Lsteps, beam_size, done_count, done_p, done_seq, done_lp, s);
 }
 
 }  // extern "C"

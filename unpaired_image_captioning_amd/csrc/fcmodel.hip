@@ -11,8 +11,12 @@
 // decode chain, but it writes every step into the teacher-forced layout above -- x_all, gates, c_buf, h_buf, the f32 logits of
 // each step, the raw tokens fed -- so that its backward (uic_fc_reward_backward) starts at RewardCriterion's gradient: the
 // criterion's row kernels turn d loss / d seq_logp into d logits in the operand dtype, and the tail of uic_fc_backward follows.
+//
+// Decoding (uic_fc_sample, uic_fc_sample_beam): the two warm-up core steps and the per-step embed -> core -> logits are here; the
+// sampling and beam buffers, how a pass starts and the beam loop are decode_internal.h's.
 #include "uic_common.h"
 #include "uic_host.h"
+#include "decode_internal.h"
 #include "../../include/uic_hip.h"
 #include <string.h>
 
@@ -37,10 +41,9 @@ struct FcLayout {
   float* dhrec; float* dc; float* dx_all; void* dx0;
   void* tA; void* tB; float* colscratch; size_t colscratch_floats; float* slab; size_t slab_bytes;
   // sampling
-  void* s_h[2]; float* s_c[2]; void* s_xt; float* s_logits; int64_t* s_it; int* s_unf; int* s_nunf;
-  // beam search bookkeeping (rows = (image, beam))
-  float* bm_cand_val; int* bm_cand_idx; int64_t* bm_seq[2]; float* bm_lp[2]; float* bm_sum; int* bm_parent;
-  int* bm_done_count; float* bm_done_p; int64_t* bm_done_seq; float* bm_done_lp;
+  void* s_h[2]; float* s_c[2]; void* s_xt; float* s_logits;
+  SampleScratch smp;    // N rows, step capacity S
+  BeamScratch beam;     // N rows, a done_count entry per row, step capacity S
   int* embed_scratch;   // uic_embed_bwd_sorted_launch
   // kept sampling pass (uic_fc_sample_train -> uic_fc_reward_backward)
   int64_t* tok;         // [N, S]: column j = the token fed at core step j + 1 (column 0 = <bos>), the layout of `labels`
@@ -101,21 +104,8 @@ FcLayout fc_layout(const uic_fc_dims& d, const uic_fc_weights* w, void* ws) {
   }
   L.s_xt = b.take(N * E * Sz);
   L.s_logits = (float*)b.take(N * V1p * 4);
-  L.s_it = (int64_t*)b.take(N * 8);
-  L.s_unf = (int*)b.take(N * 4);
-  L.s_nunf = (int*)b.take((S + 2) * UIC_NUNF_STRIPES * 4);
-  L.bm_cand_val = (float*)b.take(N * UIC_BEAM_MAX * 4);
-  L.bm_cand_idx = (int*)b.take(N * UIC_BEAM_MAX * 4);
-  for (int i = 0; i < 2; ++i) {
-    L.bm_seq[i] = (int64_t*)b.take(N * S * 8);
-    L.bm_lp[i] = (float*)b.take(N * S * 4);
-  }
-  L.bm_sum = (float*)b.take(N * 4);
-  L.bm_parent = (int*)b.take(N * 4);
-  L.bm_done_count = (int*)b.take(N * 4);
-  L.bm_done_p = (float*)b.take(N * S * 4);
-  L.bm_done_seq = (int64_t*)b.take(N * S * S * 8);
-  L.bm_done_lp = (float*)b.take(N * S * S * 4);
+  L.smp.carve(b, N, S);
+  L.beam.carve(b, N, N, S);
   L.embed_scratch = (int*)b.take(uic_embed_bwd_sorted_scratch_ints((int)N, (int)S, d.V1, d.E) * 4);
   L.tok = (int64_t*)b.take(N * S * 8);
   L.scale = (float*)b.take(N * S * 4);
@@ -367,12 +357,8 @@ int uic_fc_sample_train(const uic_fc_dims* d, const uic_fc_weights* w, const uic
   UIC_TRY(uic_fill_launch(L.h_buf, 0, NH * Sz, s));
   UIC_TRY(uic_fill_launch(L.c_buf, 0, NH * 4, s));
   UIC_TRY(uic_fill_launch(L.tok, 0, (size_t)N * S * 8, s));         // column 0: <bos> at step 1 (:183-184)
-  UIC_TRY(uic_fill_launch(L.s_it, 0, (size_t)N * 8, s));
-  UIC_TRY(uic_fill_launch(L.s_unf, 0, (size_t)N * 4, s));
-  UIC_TRY(uic_fill_launch(L.s_nunf, 0, (size_t)(S + 2) * UIC_NUNF_STRIPES * 4, s));
   const int ld = Lsteps + 1;                                         // seq / seqLogprobs are [N, L+1] (:176-177)
-  UIC_TRY(uic_fill_launch(seq, 0, (size_t)N * ld * 8, s));
-  UIC_TRY(uic_fill_launch(seq_logp, 0, (size_t)N * ld * 4, s));
+  UIC_TRY(sample_begin(L.smp, N, S, seq, seq_logp, (size_t)N * ld, s));
   for (int t = 0; t <= Lsteps; ++t) {                                // core steps 0 .. L; decisions after steps 1 .. L
     void* xt = offw(L.x_all, (size_t)t * NE, dt);
     if (t == 0) {
@@ -381,7 +367,7 @@ int uic_fc_sample_train(const uic_fc_dims* d, const uic_fc_weights* w, const uic
       g.C = xt; g.ldc = E; g.bias = w->img_embed_b;
       UIC_TRY(uic_gemm_launch(g, s));
     } else {
-      UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.s_it, 1, N, 1, 0.f, 0, 0, 0, 0, xt, s));
+      UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.smp.it, 1, N, 1, 0.f, 0, 0, 0, 0, xt, s));
     }
     // LSTMCore.dropout on next_h (:47-50) is live in train mode: the masks of uic_fc_forward(training = 1, seed)
     UIC_TRY(fc_core(*d, L, xt, w, nullptr, off(L.h_buf, t * NH, dt), L.c_buf + t * NH, L.c_buf + (t + 1) * NH,
@@ -392,18 +378,14 @@ int uic_fc_sample_train(const uic_fc_dims* d, const uic_fc_weights* w, const uic
       add_seg(g, off(L.h_buf, (t + 1) * NH, dt), H, L.logit_w, H, H);
       g.C = logits; g.ldc = V1p; g.bias = w->logit_b; g.flags = UIC_GEMM_OUT_F32;
       UIC_TRY(uic_gemm_launch(g, s));
-      UicSampleParams p;
-      memset(&p, 0, sizeof(p));
-      p.dtype = dt; p.N = N; p.V1 = V1; p.ldv = V1p; p.t = t - 1; p.L = Lsteps;
-      p.logits = logits; p.sample_max = 0; p.temperature = temperature; p.seed = seed;
-      p.seq = seq; p.seq_logp = seq_logp; p.it = L.s_it; p.unfinished = L.s_unf; p.n_unfinished = L.s_nunf;
-      p.forced = forced; p.fc_mode = 1; p.ld_out = ld;
+      UicSampleParams p = sample_params(L.smp, dt, N, V1, t - 1, Lsteps, logits, 0, temperature, 0, seed, forced, seq, seq_logp);
+      p.fc_mode = 1; p.ld_out = ld;
       UIC_TRY(uic_sample_step_launch(p, s));
       // the RAW choice: what the next step is fed (:199) and what this step's log-prob was gathered at
-      UIC_TRY(uic_copy_tokens_launch(L.s_it, 1, N, 1, L.tok + t, S, s));
+      UIC_TRY(uic_copy_tokens_launch(L.smp.it, 1, N, 1, L.tok + t, S, s));
     }
   }
-  return uic_sample_fixup_launch(N, Lsteps, ld, L.s_nunf, seq, seq_logp, s);
+  return uic_sample_fixup_launch(N, Lsteps, ld, L.smp.n_unfinished, seq, seq_logp, s);
 }
 
 int uic_fc_reward_backward(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdown_batch* b, int32_t Lsteps,
@@ -415,7 +397,7 @@ int uic_fc_reward_backward(const uic_fc_dims* d, const uic_fc_weights* w, const 
   const FcLayout L = fc_layout(*d, w, workspace);
   const int dt = d->dtype, N = d->N, V1 = d->V1, V1p = (int)vpad(V1), S = d->S, ld = Lsteps + 1;
   const void* fc_in = dt == UIC_BF16 ? L.fcT : (const void*)b->fc_feats;
-  UIC_TRY(uic_sample_reward_scale_launch(N, Lsteps, ld, L.s_nunf, dlogp, L.scale, s));
+  UIC_TRY(uic_sample_reward_scale_launch(N, Lsteps, ld, L.smp.n_unfinished, dlogp, L.scale, s));
   // d logits of decision t (core step t + 1) = (softmax - onehot(tok[:, t + 1])) * scale[:, t], straight into the operand-dtype
   // buffer the d h / dW GEMMs read: the criterion's row kernels with a per-position weight
   UicXeParams x;
@@ -447,12 +429,8 @@ int uic_fc_sample(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdo
   }
   UIC_TRY(uic_fill_launch(L.s_h[0], 0, NH * Sz, s));
   UIC_TRY(uic_fill_launch(L.s_c[0], 0, NH * 4, s));
-  UIC_TRY(uic_fill_launch(L.s_it, 0, (size_t)N * 8, s));            // <bos> at step 1 (:183-184)
-  UIC_TRY(uic_fill_launch(L.s_unf, 0, (size_t)N * 4, s));
-  UIC_TRY(uic_fill_launch(L.s_nunf, 0, (size_t)(d->S + 2) * UIC_NUNF_STRIPES * 4, s));
   const int ld = Lsteps + 1;                                         // seq / seqLogprobs are [N, L+1] (:176-177)
-  UIC_TRY(uic_fill_launch(seq, 0, (size_t)N * ld * 8, s));
-  UIC_TRY(uic_fill_launch(seq_logp, 0, (size_t)N * ld * 4, s));
+  UIC_TRY(sample_begin(L.smp, N, d->S, seq, seq_logp, (size_t)N * ld, s));   // <bos> at step 1 (:183-184)
   for (int t = 0; t <= Lsteps; ++t) {                                // core steps 0 .. L; decisions after steps 1 .. L
     const int cur = t & 1, nxt = cur ^ 1;
     if (t == 0) {
@@ -461,7 +439,7 @@ int uic_fc_sample(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdo
       g.C = L.s_xt; g.ldc = E; g.bias = w->img_embed_b;
       UIC_TRY(uic_gemm_launch(g, s));
     } else {
-      UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.s_it, 1, N, 1, 0.f, 0, 0, 0, 0, L.s_xt, s));
+      UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.smp.it, 1, N, 1, 0.f, 0, 0, 0, 0, L.s_xt, s));
     }
     UIC_TRY(fc_core(*d, L, L.s_xt, w, nullptr, L.s_h[cur], L.s_c[cur], L.s_c[nxt], L.s_h[nxt], nullptr, 0.f, 0, t, s));
     if (t >= 1) {
@@ -469,16 +447,12 @@ int uic_fc_sample(const uic_fc_dims* d, const uic_fc_weights* w, const uic_topdo
       add_seg(g, L.s_h[nxt], H, L.logit_w, H, H);
       g.C = L.s_logits; g.ldc = V1p; g.bias = w->logit_b; g.flags = UIC_GEMM_OUT_F32;
       UIC_TRY(uic_gemm_launch(g, s));
-      UicSampleParams p;
-      memset(&p, 0, sizeof(p));
-      p.dtype = dt; p.N = N; p.V1 = V1; p.ldv = V1p; p.t = t - 1; p.L = Lsteps;
-      p.logits = L.s_logits; p.sample_max = sample_max; p.temperature = temperature; p.seed = seed;
-      p.seq = seq; p.seq_logp = seq_logp; p.it = L.s_it; p.unfinished = L.s_unf; p.n_unfinished = L.s_nunf;
-      p.forced = forced; p.fc_mode = 1; p.ld_out = ld;
+      UicSampleParams p = sample_params(L.smp, dt, N, V1, t - 1, Lsteps, L.s_logits, sample_max, temperature, 0, seed, forced, seq, seq_logp);
+      p.fc_mode = 1; p.ld_out = ld;
       UIC_TRY(uic_sample_step_launch(p, s));
     }
   }
-  return uic_sample_fixup_launch(N, Lsteps, ld, L.s_nunf, seq, seq_logp, s);
+  return uic_sample_fixup_launch(N, Lsteps, ld, L.smp.n_unfinished, seq, seq_logp, s);
 }
 
 
@@ -501,13 +475,9 @@ int uic_fc_sample_beam(const uic_fc_dims* d, const uic_fc_weights* w, const uic_
   }
   UIC_TRY(uic_fill_launch(L.s_h[0], 0, NH * Sz, s));
   UIC_TRY(uic_fill_launch(L.s_c[0], 0, NH * 4, s));
-  UIC_TRY(uic_fill_launch(L.s_it, 0, (size_t)N * 8, s));            // <bos> (:151-153)
-  for (int i = 0; i < 2; ++i) {
-    UIC_TRY(uic_fill_launch(L.bm_seq[i], 0, (size_t)N * S * 8, s));
-    UIC_TRY(uic_fill_launch(L.bm_lp[i], 0, (size_t)N * S * 4, s));
-  }
-  UIC_TRY(uic_fill_launch(L.bm_sum, 0, (size_t)N * 4, s));
-  UIC_TRY(uic_fill_launch(L.bm_done_count, 0, (size_t)N * 4, s));
+  UIC_TRY(uic_fill_launch(L.smp.it, 0, (size_t)N * 8, s));          // <bos> (:151-153)
+  UicBeamParams p;
+  UIC_TRY(beam_begin(L.beam, L.s_logits, V1p, L.smp.it, N / beam_size, beam_size, S, V1, Lsteps, decoding_constraint, max_ppl, p, s));
   auto logits = [&](const void* h) -> int {
     UicGemmParams g = gemm_base(dt, N, V1);
     add_seg(g, h, H, L.logit_w, H, H);
@@ -522,28 +492,17 @@ int uic_fc_sample_beam(const uic_fc_dims* d, const uic_fc_weights* w, const uic_
     UIC_TRY(fc_core(*d, L, L.s_xt, w, nullptr, L.s_h[0], L.s_c[0], L.s_c[1], L.s_h[1], nullptr, 0.f, 0, 0, s));
   }
   // warm-up step 1: <bos> (:151-156), slot 1 -> 0; its log-probs open the search
-  UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.s_it, 1, N, 1, 0.f, 0, 0, 0, 0, L.s_xt, s));
+  UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.smp.it, 1, N, 1, 0.f, 0, 0, 0, 0, L.s_xt, s));
   UIC_TRY(fc_core(*d, L, L.s_xt, w, nullptr, L.s_h[1], L.s_c[1], L.s_c[0], L.s_h[0], nullptr, 0.f, 0, 1, s));
   UIC_TRY(logits(L.s_h[0]));
-  UicBeamParams p;
-  memset(&p, 0, sizeof(p));
-  p.n_img = N / beam_size; p.B = beam_size; p.L = Lsteps; p.V1 = V1; p.ldv = V1p;
-  p.decoding_constraint = decoding_constraint; p.max_ppl = max_ppl;
-  p.logits = L.s_logits; p.cand_val = L.bm_cand_val; p.cand_idx = L.bm_cand_idx;
-  p.beam_seq_hist[0] = L.bm_seq[0]; p.beam_seq_hist[1] = L.bm_seq[1]; p.beam_lp_hist[0] = L.bm_lp[0]; p.beam_lp_hist[1] = L.bm_lp[1];
-  p.beam_sum = L.bm_sum; p.parent = L.bm_parent; p.it = L.s_it;
-  p.done_count = L.bm_done_count; p.done_p = L.bm_done_p; p.done_seq = L.bm_done_seq; p.done_lp = L.bm_done_lp;
-  for (int t = 0; t < Lsteps; ++t) {
-    p.t = t;
-    UIC_TRY(uic_beam_step_launch(p, s));
-    if (t + 1 == Lsteps) break;
-    UIC_TRY(uic_beam_gather_launch(dt, L.bm_parent, N, beam_size, H, L.s_h[0], L.s_h[1], nullptr, nullptr, L.s_c[0], L.s_c[1], nullptr, nullptr, s));
-    // get_logprobs_state (:126-134): embed -> core -> log_softmax(logit), slot 1 -> 0
-    UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.s_it, 1, N, 1, 0.f, 0, 0, 0, 0, L.s_xt, s));
-    UIC_TRY(fc_core(*d, L, L.s_xt, w, nullptr, L.s_h[1], L.s_c[1], L.s_c[0], L.s_h[0], nullptr, 0.f, 0, t + 2, s));
-    UIC_TRY(logits(L.s_h[0]));
-  }
-  return uic_beam_final_launch(p, seq, seq_logp, s);
+  auto advance = [&](int t_next) -> int {
+    UIC_TRY(uic_beam_gather_launch(dt, p.parent, N, beam_size, H, L.s_h[0], L.s_h[1], nullptr, nullptr, L.s_c[0], L.s_c[1], nullptr, nullptr, s));
+    // get_logprobs_state (:126-134): embed -> core -> log_softmax(logit), slot 1 -> 0; core step t_next + 1 behind the two warm-up steps
+    UIC_TRY(uic_embed_fwd_launch(dt, w->embed_w, V1, E, L.smp.it, 1, N, 1, 0.f, 0, 0, 0, 0, L.s_xt, s));
+    UIC_TRY(fc_core(*d, L, L.s_xt, w, nullptr, L.s_h[1], L.s_c[1], L.s_c[0], L.s_h[0], nullptr, 0.f, 0, t_next + 1, s));
+    return logits(L.s_h[0]);
+  };
+  return beam_search(p, Lsteps, advance, s, seq, seq_logp);
 }
 
 }  // extern "C"

@@ -1,10 +1,12 @@
 // Decoding with the TopDown captioner: the decode step on the sampling buffers, greedy / multinomial sampling (also in the
 // training layout, for the self-critical step), one get_logprobs_state, beam search, and the ensemble of several captioners.
+// The sampling and beam bookkeeping (how a pass starts, the beam loop, the done-list export) is decode_internal.h's; this file
+// supplies the decode step, the recurrent state's clearing and gathering, and -- for the ensemble -- the loop over members.
 #include "topdown_internal.h"
 
 namespace topdown {
 
-// One decode step of AttModel.get_logprobs_state (:158-165) on the sampling buffers: embedding of L.s_it, both LSTM cells,
+// One decode step of AttModel.get_logprobs_state (:158-165) on the sampling buffers: embedding of L.smp.it, both LSTM cells,
 // attention, logits into L.s_logits; recurrent state read from slot `cur`, written to slot `nxt`.
 int decode_step(const uic_topdown_dims& d, const uic_topdown_weights* w, const Derived& dv, const uic_topdown_batch* b, const Layout& L,
                 int cur, int nxt, int t, float drop_p, unsigned seed, hipStream_t s, bool train_mode, bool xt_ready) {
@@ -12,7 +14,7 @@ int decode_step(const uic_topdown_dims& d, const uic_topdown_weights* w, const D
   const int N = d.N, H = d.H, E = d.E, V1 = d.V1;
   const int V1p = (int)vpad(V1);
   // (xt_ready: the sampling kernel of the previous step already wrote this step's embedding rows into L.s_xt)
-  if (!xt_ready) UIC_TRY(uic_embed_fwd_t_launch(dt, dv.embed_w, dt, V1, E, L.s_it, 1, N, 1, drop_p, seed, UIC_SITE_EMBED, (size_t)t * N * E, 1, L.s_xt, s));
+  if (!xt_ready) UIC_TRY(uic_embed_fwd_t_launch(dt, dv.embed_w, dt, V1, E, L.smp.it, 1, N, 1, drop_p, seed, UIC_SITE_EMBED, (size_t)t * N * E, 1, L.s_xt, s));
   UIC_TRY(uic_gemm_launch(att_lstm_gemm(d, w, dv, L, L.s_h_lang[cur], L.s_h_att[cur], L.s_c_att[cur], L.s_c_att[nxt], L.s_h_att[nxt], t,
                                         L.s_xt, false), s));
   UIC_TRY(attention_step(d, w, dv, b, L, L.s_h_att[nxt], L.s_atth, L.s_alpha, L.s_ctx, s));
@@ -39,54 +41,23 @@ using namespace topdown;
 
 namespace {
 
-// zero recurrent state in slot 0 of the sampling buffers, <bos> = 0 as the first input (AttModel.py:214-215, :187)
-int decode_state_zero(const Layout& L, size_t NH, size_t S, int N, hipStream_t s) {
+// zero recurrent state in slot 0 of the sampling buffers (AttModel.py:214-215, :187); the first input <bos> = 0 is sample_begin's,
+// or the beam drivers' own fill
+int decode_state_zero(const Layout& L, size_t NH, size_t S, hipStream_t s) {
   UIC_TRY(uic_fill_launch(L.s_h_att[0], 0, NH * S, s));
   UIC_TRY(uic_fill_launch(L.s_h_lang[0], 0, NH * S, s));
   UIC_TRY(uic_fill_launch(L.s_c_att[0], 0, NH * 4, s));
-  UIC_TRY(uic_fill_launch(L.s_c_lang[0], 0, NH * 4, s));
-  return uic_fill_launch(L.s_it, 0, (size_t)N * 8, s);
-}
-// the sampling kernel's unfinished flags and counters
-int unfinished_zero(const Layout& L, int N, int T, hipStream_t s) {
-  UIC_TRY(uic_fill_launch(L.s_unf, 0, (size_t)N * 4, s));
-  return uic_fill_launch(L.s_nunf, 0, (size_t)(T + 2) * UIC_NUNF_STRIPES * 4, s);
-}
-// step t of a sampling pass over `logits`; token, flags and counters live in L's sampling buffers
-UicSampleParams sample_params(int dtype, int N, int V1, int t, int Lsteps, const float* logits, const Layout& L, int sample_max,
-                              float temperature, int decoding_constraint, unsigned seed, const int64_t* forced, int64_t* seq,
-                              float* seq_logp) {
-  UicSampleParams p;
-  memset(&p, 0, sizeof(p));
-  p.dtype = dtype; p.N = N; p.V1 = V1; p.ldv = (int)vpad(V1); p.t = t; p.L = Lsteps;
-  p.logits = logits; p.sample_max = sample_max; p.temperature = temperature; p.seed = seed;
-  p.decoding_constraint = decoding_constraint;
-  p.seq = seq; p.seq_logp = seq_logp; p.it = L.s_it; p.unfinished = L.s_unf; p.n_unfinished = L.s_nunf;
-  p.forced = forced;
-  return p;
+  return uic_fill_launch(L.s_c_lang[0], 0, NH * 4, s);
 }
 // the next step's embedding rows ride in the sampling kernel (one launch less per step)
 void sample_embeds_next(UicSampleParams& p, const uic_topdown_dims& d, const Derived& dv, float drop_p, void* xt_out) {
   p.embed_table = dv.embed_w; p.embed_table_dtype = d.dtype; p.embed_V1 = d.V1; p.embed_E = d.E; p.embed_drop_p = drop_p; p.embed_site = UIC_SITE_EMBED;
   p.embed_idx_base = (size_t)(p.t + 1) * d.N * d.E; p.xt_out = xt_out;
 }
-// beam search bookkeeping of L cleared, the beam kernels' parameters over it
-int beam_begin(const Layout& L, int N, int T, int V1, int Lsteps, int beam_size, int decoding_constraint, int max_ppl, UicBeamParams& p,
-               hipStream_t s) {
-  for (int i = 0; i < 2; ++i) {
-    UIC_TRY(uic_fill_launch(L.bm_seq[i], 0, (size_t)N * T * 8, s));
-    UIC_TRY(uic_fill_launch(L.bm_lp[i], 0, (size_t)N * T * 4, s));
-  }
-  UIC_TRY(uic_fill_launch(L.bm_sum, 0, (size_t)N * 4, s));
-  UIC_TRY(uic_fill_launch(L.bm_done_count, 0, (size_t)N * 4, s));
-  memset(&p, 0, sizeof(p));
-  p.n_img = N / beam_size; p.B = beam_size; p.L = Lsteps; p.V1 = V1; p.ldv = (int)vpad(V1);
-  p.decoding_constraint = decoding_constraint; p.max_ppl = max_ppl;
-  p.logits = L.s_logits; p.cand_val = L.bm_cand_val; p.cand_idx = L.bm_cand_idx;
-  p.beam_seq_hist[0] = L.bm_seq[0]; p.beam_seq_hist[1] = L.bm_seq[1]; p.beam_lp_hist[0] = L.bm_lp[0]; p.beam_lp_hist[1] = L.bm_lp[1];
-  p.beam_sum = L.bm_sum; p.parent = L.bm_parent; p.it = L.s_it;
-  p.done_count = L.bm_done_count; p.done_p = L.bm_done_p; p.done_seq = L.bm_done_seq; p.done_lp = L.bm_done_lp;
-  return UIC_OK;
+// the search over L's sampling buffers: N = images x beam_size rows, step capacity T
+int topdown_beam_begin(const uic_topdown_dims& d, const Layout& L, int Lsteps, int beam_size, int decoding_constraint, int max_ppl,
+                        UicBeamParams& p, hipStream_t s) {
+  return beam_begin(L.beam, L.s_logits, (int)vpad(d.V1), L.smp.it, d.N / beam_size, beam_size, d.T, d.V1, Lsteps, decoding_constraint, max_ppl, p, s);
 }
 
 }  // namespace
@@ -121,12 +92,12 @@ int uic_topdown_sample(const uic_topdown_dims* d, const uic_topdown_weights* w, 
       return st.decode_persist(Lsteps, sample_max, forced, false, seq, seq_logp, s);
     }
   }
-  UIC_TRY(decode_state_zero(L, NH, S, N, s));
-  UIC_TRY(unfinished_zero(L, N, d->T, s));
+  UIC_TRY(decode_state_zero(L, NH, S, s));
+  UIC_TRY(sample_begin(L.smp, N, d->T, nullptr, nullptr, 0, s));
   for (int t = 0; t < Lsteps; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
     UIC_TRY(decode_step(*d, w, dv, b, L, cur, nxt, t, drop_p, seed, s, (training & 1) != 0, t > 0));
-    UicSampleParams p = sample_params(dt, N, V1, t, Lsteps, L.s_logits, L, sample_max, temperature, decoding_constraint, seed, forced, seq, seq_logp);
+    UicSampleParams p = sample_params(L.smp, dt, N, V1, t, Lsteps, L.s_logits, sample_max, temperature, decoding_constraint, seed, forced, seq, seq_logp);
     if (t + 1 < Lsteps) sample_embeds_next(p, *d, dv, drop_p, L.s_xt);
     UIC_TRY(uic_sample_step_launch(p, s));
   }
@@ -158,15 +129,14 @@ int uic_topdown_sample_train(const uic_topdown_dims* d, const uic_topdown_weight
   UIC_TRY(wait_refresh(s));
   if (st.decode_persist_ok(sample_max, temperature, decoding_constraint))
     return st.decode_persist(Lsteps, sample_max, forced, true, seq, seq_logp, s);
-  UIC_TRY(uic_fill_launch(L.s_it, 0, (size_t)N * 8, s));       // <bos> = 0 (AttModel.py:214-215)
-  UIC_TRY(unfinished_zero(L, N, d->T, s));
+  UIC_TRY(sample_begin(L.smp, N, d->T, nullptr, nullptr, 0, s));   // <bos> = 0 (AttModel.py:214-215)
   for (int t = 0; t < Lsteps; ++t) {
     if (t == 0)   // (later steps: written by the previous step's sampling kernel)
-      UIC_TRY(uic_embed_fwd_t_launch(st.dt, st.dv.embed_w, st.dt, st.V1, st.E, L.s_it, 1, N, 1, st.drop_p, seed, UIC_SITE_EMBED,
+      UIC_TRY(uic_embed_fwd_t_launch(st.dt, st.dv.embed_w, st.dt, st.V1, st.E, L.smp.it, 1, N, 1, st.drop_p, seed, UIC_SITE_EMBED,
                                    (size_t)t * N * st.E, 1, offw(L.xt_all, (size_t)t * N * st.E, st.dt), s));
     UIC_TRY(st.fwd_step(t, s, true));
     UIC_TRY(st.logits_rows_now(t, t + 1, s));
-    UicSampleParams p = sample_params(st.dt, N, st.V1, t, Lsteps, L.logits + (size_t)t * N * st.V1p, L, sample_max, temperature, decoding_constraint,
+    UicSampleParams p = sample_params(L.smp, st.dt, N, st.V1, t, Lsteps, L.logits + (size_t)t * N * st.V1p, sample_max, temperature, decoding_constraint,
                                       seed, forced, seq, seq_logp);
     if (t + 1 < Lsteps) sample_embeds_next(p, st.d, st.dv, st.drop_p, offw(L.xt_all, (size_t)(t + 1) * N * st.E, st.dt));
     UIC_TRY(uic_sample_step_launch(p, s));
@@ -196,7 +166,7 @@ int uic_topdown_logprobs_state(const uic_topdown_dims* d, const uic_topdown_weig
   UIC_TRY(uic_cast_f32_launch(dt, h_in + N * H, L.s_h_lang[0], N * H, s));
   UIC_TRY(uic_copy_launch(L.s_c_att[0], c_in, N * H * 4, s));
   UIC_TRY(uic_copy_launch(L.s_c_lang[0], c_in + N * H, N * H * 4, s));
-  UIC_TRY(uic_copy_launch(L.s_it, it, N * 8, s));
+  UIC_TRY(uic_copy_launch(L.smp.it, it, N * 8, s));
   uic_topdown_batch b;
   memset(&b, 0, sizeof(b));
   b.att_masks = att_masks;
@@ -223,11 +193,7 @@ int uic_topdown_beam_done_lists(const uic_topdown_dims* d, void* workspace, int3
   UIC_REQUIRE(beam_size >= 1 && d->N % beam_size == 0 && Lsteps >= 1 && Lsteps <= d->T, "beam_done_lists: bad sizes");
   hipStream_t s = (hipStream_t)stream;
   const Layout L = make_layout(*d, workspace);
-  const size_t n_img = (size_t)d->N / beam_size, LB = (size_t)Lsteps * beam_size;
-  UIC_TRY(uic_copy_launch(done_count, L.bm_done_count, n_img * 4, s));
-  UIC_TRY(uic_copy_launch(done_p, L.bm_done_p, n_img * LB * 4, s));
-  UIC_TRY(uic_copy_launch(done_seq, L.bm_done_seq, n_img * LB * Lsteps * 8, s));
-  return uic_copy_launch(done_lp, L.bm_done_lp, n_img * LB * Lsteps * 4, s);
+  return beam_done_lists(L.beam, (size_t)d->N / beam_size, Lsteps, beam_size, done_count, done_p, done_seq, done_lp, s);
 }
 
 int uic_topdown_sample_beam(const uic_topdown_dims* d, const uic_topdown_weights* w, const void* derived,
@@ -243,24 +209,22 @@ int uic_topdown_sample_beam(const uic_topdown_dims* d, const uic_topdown_weights
   const Layout L = make_layout(*d, workspace);
   const Derived dv = make_derived(*d, w, (void*)derived);
   const int dt = d->dtype;
-  const int N = d->N, H = d->H, V1 = d->V1, T = d->T;
+  const int N = d->N, H = d->H;
   const size_t S = uic_dtype_size(dt), NH = (size_t)N * H;
   const void *fc_in, *att_in;
   UIC_TRY(prepare_features(*d, w, dv, b, L, 0, 0.f, 0, &fc_in, &att_in, s));      // eval mode, like eval_utils.eval_split
   UIC_TRY(wait_refresh(s));
-  UIC_TRY(decode_state_zero(L, NH, S, N, s));                  // <bos> for every beam row
+  UIC_TRY(decode_state_zero(L, NH, S, s));
+  UIC_TRY(uic_fill_launch(L.smp.it, 0, (size_t)N * 8, s));     // <bos> for every beam row
   UicBeamParams p;
-  UIC_TRY(beam_begin(L, N, T, V1, Lsteps, beam_size, decoding_constraint, max_ppl, p, s));
+  UIC_TRY(topdown_beam_begin(*d, L, Lsteps, beam_size, decoding_constraint, max_ppl, p, s));
   UIC_TRY(decode_step(*d, w, dv, b, L, 0, 1, 0, 0.f, 0, s));   // logprobs after <bos> (AttModel.py:184-190)
-  for (int t = 0; t < Lsteps; ++t) {
-    p.t = t;
-    UIC_TRY(uic_beam_step_launch(p, s));
-    if (t + 1 == Lsteps) break;                                // (the reference's last get_logprobs_state is never used)
-    UIC_TRY(uic_beam_gather_launch(dt, L.bm_parent, N, beam_size, H, L.s_h_att[1], L.s_h_att[0], L.s_h_lang[1], L.s_h_lang[0],
+  auto advance = [&](int t_next) -> int {
+    UIC_TRY(uic_beam_gather_launch(dt, p.parent, N, beam_size, H, L.s_h_att[1], L.s_h_att[0], L.s_h_lang[1], L.s_h_lang[0],
                                    L.s_c_att[1], L.s_c_att[0], L.s_c_lang[1], L.s_c_lang[0], s));
-    UIC_TRY(decode_step(*d, w, dv, b, L, 0, 1, t + 1, 0.f, 0, s));
-  }
-  return uic_beam_final_launch(p, seq, seq_logp, s);
+    return decode_step(*d, w, dv, b, L, 0, 1, t_next, 0.f, 0, s);
+  };
+  return beam_search(p, Lsteps, advance, s, seq, seq_logp);
 }
 
 }  // extern "C"
@@ -269,12 +233,12 @@ int uic_topdown_sample_beam(const uic_topdown_dims* d, const uic_topdown_weights
 // Every member keeps its own dims / weights / derived copies / workspace and runs the decode step of the single-model chain on
 // the caller's stream; ensemble_logmean_kernel (ensemble.hip) then folds the M rows of step logits into member 0's, and the
 // single model's sampling / beam kernels go on from there as if member 0 had produced them.  The chosen token needs no copy:
-// every member's embedding lookup reads member 0's `s_it`.
+// every member's embedding lookup reads member 0's token buffer.
 namespace {
 
-// L is make_layout() of the member's own workspace with ONE field patched: L.s_it of every member is member 0's.  decode_step
-// reads the input token from L.s_it only (its embedding lookup; the ensemble path never passes xt_ready), and the sampling / beam
-// kernels write it to member 0's: the members' own s_it buffers stay unused, and nothing else of a Layout may be shared.
+// L is make_layout() of the member's own workspace with ONE field patched: L.smp.it of every member is member 0's.  decode_step
+// reads the input token from L.smp.it only (its embedding lookup; the ensemble path never passes xt_ready), and the sampling / beam
+// kernels write it to member 0's: the members' own token buffers stay unused, and nothing else of a Layout may be shared.
 struct Member {
   const uic_topdown_dims* d; const uic_topdown_weights* w; const uic_topdown_batch* b;
   Derived dv; Layout L;
@@ -301,12 +265,12 @@ int ensemble_members(const char* what, int M, const uic_topdown_dims* const* d, 
     mem[m].d = d[m]; mem[m].w = w[m]; mem[m].b = b[m];
     mem[m].L = make_layout(*d[m], workspace[m]);
     mem[m].dv = make_derived(*d[m], w[m], (void*)derived[m]);
-    mem[m].L.s_it = mem[0].L.s_it;
+    mem[m].L.smp.it = mem[0].L.smp.it;
   }
   return UIC_OK;
 }
 
-// eval-mode features and the zero initial state of every member, <bos> as the first input
+// eval-mode features and the zero initial state of every member
 int ensemble_begin(int M, Member* mem, hipStream_t s) {
   for (int m = 0; m < M; ++m) {
     const void *fc_in, *att_in;
@@ -318,7 +282,7 @@ int ensemble_begin(int M, Member* mem, hipStream_t s) {
     const size_t NH = (size_t)mem[m].d->N * mem[m].d->H, S = uic_dtype_size(mem[m].d->dtype);
     UIC_TRY(uic_zero4_launch(L.s_h_att[0], NH * S, L.s_h_lang[0], NH * S, L.s_c_att[0], NH * 4, L.s_c_lang[0], NH * 4, s));
   }
-  return uic_fill_launch(mem[0].L.s_it, 0, (size_t)mem[0].d->N * 8, s);
+  return UIC_OK;
 }
 
 // one get_logprobs_state of the ensemble (AttEnsemble.py:48-55): states slot `cur` -> `nxt`, combined log-probs into member 0's s_logits
@@ -352,12 +316,12 @@ int uic_topdown_ensemble_sample(int32_t M, const uic_topdown_dims* const* d, con
   bool all_bf16 = true;
   for (int m = 0; m < M; ++m) all_bf16 = all_bf16 && d[m]->dtype == UIC_BF16;
   UIC_TRY(ensemble_begin(M, mem, s));
-  UIC_TRY(unfinished_zero(L0, N, d[0]->T, s));
+  UIC_TRY(sample_begin(L0.smp, N, d[0]->T, nullptr, nullptr, 0, s));
   for (int t = 0; t < Lsteps; ++t) {
     const int cur = t & 1, nxt = cur ^ 1;
     UIC_TRY(ensemble_step(M, mem, cur, nxt, t, s));
     // (the hardware exponential of the bf16 sampling kernel only when no member is an f32 parity model)
-    const UicSampleParams p = sample_params(all_bf16 ? UIC_BF16 : UIC_F32, N, V1, t, Lsteps, L0.s_logits, L0, sample_max, temperature,
+    const UicSampleParams p = sample_params(L0.smp, all_bf16 ? UIC_BF16 : UIC_F32, N, V1, t, Lsteps, L0.s_logits, sample_max, temperature,
                                             decoding_constraint, seed, forced, seq, seq_logp);
     UIC_TRY(uic_sample_step_launch(p, s));
   }
@@ -375,23 +339,21 @@ int uic_topdown_ensemble_sample_beam(int32_t M, const uic_topdown_dims* const* d
   UIC_REQUIRE(d[0]->N % beam_size == 0, "ensemble_sample_beam: N=%d rows must be images x beam_size=%d (every image replicated beam_size times)", d[0]->N, beam_size);
   hipStream_t s = (hipStream_t)stream;
   const Layout& L0 = mem[0].L;
-  const int N = d[0]->N, V1 = d[0]->V1, T = d[0]->T;
+  const int N = d[0]->N;
   UIC_TRY(ensemble_begin(M, mem, s));
+  UIC_TRY(uic_fill_launch(L0.smp.it, 0, (size_t)N * 8, s));    // <bos> for every beam row
   UicBeamParams p;
-  UIC_TRY(beam_begin(L0, N, T, V1, Lsteps, beam_size, decoding_constraint, max_ppl, p, s));
+  UIC_TRY(topdown_beam_begin(*d[0], L0, Lsteps, beam_size, decoding_constraint, max_ppl, p, s));
   UIC_TRY(ensemble_step(M, mem, 0, 1, 0, s));                  // logprobs after <bos> (AttEnsemble.py:88-89)
-  for (int t = 0; t < Lsteps; ++t) {
-    p.t = t;
-    UIC_TRY(uic_beam_step_launch(p, s));
-    if (t + 1 == Lsteps) break;                                // (the reference's last get_logprobs_state is never used)
-    for (int m = 0; m < M; ++m) {                              // every member's states follow the surviving parents (CaptionModel.py:90-92)
+  auto advance = [&](int t_next) -> int {
+    for (int m = 0; m < M; ++m) {                              // every member's states follow the surviving parents
       const Layout& L = mem[m].L;
-      UIC_TRY(uic_beam_gather_launch(d[m]->dtype, L0.bm_parent, N, beam_size, d[m]->H, L.s_h_att[1], L.s_h_att[0], L.s_h_lang[1], L.s_h_lang[0],
+      UIC_TRY(uic_beam_gather_launch(d[m]->dtype, p.parent, N, beam_size, d[m]->H, L.s_h_att[1], L.s_h_att[0], L.s_h_lang[1], L.s_h_lang[0],
                                      L.s_c_att[1], L.s_c_att[0], L.s_c_lang[1], L.s_c_lang[0], s));
     }
-    UIC_TRY(ensemble_step(M, mem, 0, 1, t + 1, s));
-  }
-  return uic_beam_final_launch(p, seq, seq_logp, s);
+    return ensemble_step(M, mem, 0, 1, t_next, s);
+  };
+  return beam_search(p, Lsteps, advance, s, seq, seq_logp);
 }
 
 }  // extern "C"

@@ -4,6 +4,7 @@
 #pragma once
 #include "uic_common.h"
 #include "uic_host.h"
+#include "decode_internal.h"
 #include "../../include/uic_hip.h"
 #include <string.h>
 #include <stdlib.h>
@@ -59,11 +60,9 @@ struct Layout {
   // sampling
   void* s_h_att[2]; void* s_h_lang[2]; float* s_c_att[2]; float* s_c_lang[2];
   void* s_xt; float* s_atth; float* s_alpha; void* s_ctx; void* s_hdrop; float* s_logits;
-  int64_t* s_it; int* s_unf; int* s_nunf;
+  SampleScratch smp;                         // input token, unfinished flags and counters [N], [N], step capacity T
   float* dec_part; int* dec_tok; void* dec_embed_relu;   // persistent decode (rnn_persist.hip): per-workgroup logit partials, exchanged tokens, relu(embed) in bf16
-  // beam search bookkeeping (rows = (image, beam); sizes depend on N and T only)
-  float* bm_cand_val; int* bm_cand_idx; int64_t* bm_seq[2]; float* bm_lp[2]; float* bm_sum; int* bm_parent;
-  int* bm_done_count; float* bm_done_p; int64_t* bm_done_seq; float* bm_done_lp;
+  BeamScratch beam;                          // beam search bookkeeping: N rows, a done_count entry per row, step capacity T
   size_t total;
 };
 Layout make_layout(const uic_topdown_dims& d, void* ws);

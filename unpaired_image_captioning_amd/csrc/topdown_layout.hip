@@ -145,24 +145,11 @@ Layout make_layout(const uic_topdown_dims& d, void* ws) {
   L.s_ctx = b.take(N * H * S);
   L.s_hdrop = b.take(N * H * S);
   L.s_logits = (float*)b.take(N * V1p * 4);
-  L.s_it = (int64_t*)b.take(N * 8);
-  L.s_unf = (int*)b.take(N * 4);
-  L.s_nunf = (int*)b.take((T + 2) * UIC_NUNF_STRIPES * 4);
+  L.smp.carve(b, N, T);
   L.dec_part = (float*)b.take(uic_rnn_decode_part_floats((int)N) * 4);
   L.dec_tok = (int*)b.take(N * 4);
   L.dec_embed_relu = b.take(V1 * E * 2);
-  L.bm_cand_val = (float*)b.take(N * UIC_BEAM_MAX * 4);
-  L.bm_cand_idx = (int*)b.take(N * UIC_BEAM_MAX * 4);
-  for (int i = 0; i < 2; ++i) {
-    L.bm_seq[i] = (int64_t*)b.take(N * T * 8);
-    L.bm_lp[i] = (float*)b.take(N * T * 4);
-  }
-  L.bm_sum = (float*)b.take(N * 4);
-  L.bm_parent = (int*)b.take(N * 4);
-  L.bm_done_count = (int*)b.take(N * 4);
-  L.bm_done_p = (float*)b.take(N * T * 4);
-  L.bm_done_seq = (int64_t*)b.take(N * T * T * 8);
-  L.bm_done_lp = (float*)b.take(N * T * T * 4);
+  L.beam.carve(b, N, N, T);
   L.row_order = (int*)b.take(N * 4);
   L.row_rank = (int*)b.take(N * 4);
   L.unfinished = (int*)b.take((T + 1) * 4);

@@ -156,7 +156,7 @@ int Step::decode_persist(int Lsteps, int sample_max, const int64_t* forced, bool
   p.dec_xt_drop = drop_p; p.dec_xt_all = keep ? L.xt_all : nullptr;
   p.dec_logit_w = dv.logit_w; p.dec_logit_b = w->logit_b; p.dec_V1 = V1; p.dec_V1p = V1p;
   p.dec_logits = keep ? L.logits : L.s_logits; p.dec_logits_step = keep ? (size_t)N * V1p : 0;
-  p.dec_part = L.dec_part; p.dec_tok = L.dec_tok; p.dec_unf = L.s_unf;
+  p.dec_part = L.dec_part; p.dec_tok = L.dec_tok; p.dec_unf = L.smp.unfinished;
   p.dec_seq = seq; p.dec_seq_logp = seq_logp; p.dec_ld_out = Lsteps;
   p.dec_forced = sample_max ? nullptr : forced; p.dec_ld_forced = Lsteps;
   p.dec_sample_max = sample_max; p.dec_draw_seed = seed;

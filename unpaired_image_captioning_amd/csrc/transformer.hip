@@ -6,7 +6,9 @@
 //                         added to the std -- not nn.LayerNorm.  One wave per row, the row read once into registers.
 //   mha_fwd_kernel        MultiHeadedAttention's `attention` (:178-188) for short sequences: one workgroup per (row, head),
 //                         that head's whole K and V in LDS as f32, scores / softmax in f32, no [B, h, Sq, Sk] tensor in memory.
-// Everything else is the project's GEMM (every nn.Linear), its BatchNorm operators (att_embed), sampling.hip and beam.hip.
+// Everything else is the project's GEMM (every nn.Linear), its BatchNorm operators (att_embed), sampling.hip and beam.hip -- the
+// last two through decode_internal.h, which owns their buffers, the start of a pass and the beam loop; the beam driver here
+// supplies the step and re-threads the K/V cache by the surviving parents.
 //
 // Layout of the sequencers: the residual stream x stays f32; LayerNorm writes the GEMM operand (operand dtype); the output
 // projections of attention and of the FFN accumulate into x (UIC_GEMM_ACCUM | UIC_GEMM_OUT_F32).  The three input projections
@@ -16,6 +18,7 @@
 // a step computes only the new position.  The source-attention K / V of each layer are projected once per call.
 #include "uic_common.h"
 #include "uic_host.h"
+#include "decode_internal.h"
 #include "../../include/uic_hip.h"
 #include <math.h>
 #include <string.h>
@@ -299,9 +302,8 @@ struct TfLayout {
   float* x_dec;      // [rows T, dm]
   float* logits;     // [rows T, V1p]
   void* cache[2];    // [rows][layers][T][3 dm] q | k | v of every decoded position (two generations for the beam re-threading)
-  int64_t* it; int* unf; int* nunf;
-  float* bm_cand_val; int* bm_cand_idx; int64_t* bm_seq[2]; float* bm_lp[2]; float* bm_sum; int* bm_parent;
-  int* bm_done_count; float* bm_done_p; int64_t* bm_done_seq; float* bm_done_lp;
+  SampleScratch smp; // rows = N beam, step capacity T
+  BeamScratch beam;  // the same rows, a done_count entry per image, step capacity T
   size_t total;
 };
 
@@ -331,21 +333,8 @@ TfLayout tf_layout(const uic_transformer_dims& d, void* ws) {
   L.x_dec = (float*)b.take(Md * dm * 4);
   L.logits = (float*)b.take(Md * V1p * 4);
   for (int i = 0; i < 2; ++i) L.cache[i] = b.take(rows * d.layers * T * 3 * dm * Sz);
-  L.it = (int64_t*)b.take(rows * 8);
-  L.unf = (int*)b.take(rows * 4);
-  L.nunf = (int*)b.take((T + 2) * UIC_NUNF_STRIPES * 4);
-  L.bm_cand_val = (float*)b.take(rows * UIC_BEAM_MAX * 4);
-  L.bm_cand_idx = (int*)b.take(rows * UIC_BEAM_MAX * 4);
-  for (int i = 0; i < 2; ++i) {
-    L.bm_seq[i] = (int64_t*)b.take(rows * T * 8);
-    L.bm_lp[i] = (float*)b.take(rows * T * 4);
-  }
-  L.bm_sum = (float*)b.take(rows * 4);
-  L.bm_parent = (int*)b.take(rows * 4);
-  L.bm_done_count = (int*)b.take(N * 4);
-  L.bm_done_p = (float*)b.take(rows * T * 4);
-  L.bm_done_seq = (int64_t*)b.take(rows * T * T * 8);
-  L.bm_done_lp = (float*)b.take(rows * T * T * 4);
+  L.smp.carve(b, rows, T);
+  L.beam.carve(b, rows, N, T);
   L.total = (b.off + 255) & ~(size_t)255;
   return L;
 }
@@ -498,9 +487,9 @@ struct Tf {
   int generator(int M) const {   // Generator.proj (:60-68); the log-softmax is the consumer's
     return lin(dt, M, d.V1, dm, L.xn, dm, v.gen_w, dm, L.logits, V1p, w->gen_b, UIC_GEMM_OUT_F32, s);
   }
-  // one decoding step: embed the rows' input tokens (L.it) at position t, the stack against the cache, the logits
+  // one decoding step: embed the rows' input tokens (L.smp.it) at position t, the stack against the cache, the logits
   int step(int rows, int t, void* cache, const unsigned char* kmask_rows, int src_div) const {
-    UIC_TRY(embed(L.it, 1, rows, 1, t));
+    UIC_TRY(embed(L.smp.it, 1, rows, 1, t));
     UIC_TRY(decoder(rows, 1, t, cache, nullptr, kmask_rows, src_div));
     return generator(rows);
   }
@@ -631,19 +620,10 @@ int uic_transformer_sample(const uic_transformer_dims* d, const uic_transformer_
   const TfLayout& L = tf.L;
   const int N = d->N;
   UIC_TRY(tf.encode(att_feats, att_masks, nullptr));
-  UIC_TRY(uic_fill_launch(L.it, 0, (size_t)N * 8, s));                // <bos> = 0 (:539-540)
-  UIC_TRY(uic_fill_launch(L.unf, 0, (size_t)N * 4, s));
-  UIC_TRY(uic_fill_launch(L.nunf, 0, (size_t)(d->T + 2) * UIC_NUNF_STRIPES * 4, s));
-  UIC_TRY(uic_fill_launch(seq, 0, (size_t)N * Lsteps * 8, s));
-  UIC_TRY(uic_fill_launch(seq_logp, 0, (size_t)N * Lsteps * 4, s));
+  UIC_TRY(sample_begin(L.smp, N, d->T, seq, seq_logp, (size_t)N * Lsteps, s));   // <bos> = 0 (:539-540)
   for (int t = 0; t < Lsteps; ++t) {
     UIC_TRY(tf.step(N, t, L.cache[0], L.kmask, 1));
-    UicSampleParams p;
-    memset(&p, 0, sizeof(p));
-    p.dtype = d->dtype; p.N = N; p.V1 = d->V1; p.ldv = tf.V1p; p.t = t; p.L = Lsteps;
-    p.logits = L.logits; p.sample_max = sample_max; p.temperature = temperature; p.seed = seed;
-    p.seq = seq; p.seq_logp = seq_logp; p.it = L.it; p.unfinished = L.unf; p.n_unfinished = L.nunf;
-    UIC_TRY(uic_sample_step_launch(p, s));
+    UIC_TRY(uic_sample_step_launch(sample_params(L.smp, d->dtype, N, d->V1, t, Lsteps, L.logits, sample_max, temperature, 0, seed, nullptr, seq, seq_logp), s));
   }
   return UIC_OK;
 }
@@ -662,35 +642,20 @@ int uic_transformer_sample_beam(const uic_transformer_dims* d, const uic_transfo
   const int N = d->N, B = beam_size, rows = N * B, T = d->T;
   UIC_TRY(tf.encode(att_feats, att_masks, nullptr));
   const unsigned char* kmask_rows = B > 1 ? L.kmask_rep : L.kmask;
-  UIC_TRY(uic_fill_launch(L.it, 0, (size_t)rows * 8, s));              // <bos> on every beam (:464)
-  for (int i = 0; i < 2; ++i) {
-    UIC_TRY(uic_fill_launch(L.bm_seq[i], 0, (size_t)rows * T * 8, s));
-    UIC_TRY(uic_fill_launch(L.bm_lp[i], 0, (size_t)rows * T * 4, s));
-  }
-  UIC_TRY(uic_fill_launch(L.bm_sum, 0, (size_t)rows * 4, s));
-  UIC_TRY(uic_fill_launch(L.bm_done_count, 0, (size_t)N * 4, s));
+  UIC_TRY(uic_fill_launch(L.smp.it, 0, (size_t)rows * 8, s));          // <bos> on every beam (:464)
   UicBeamParams p;
-  memset(&p, 0, sizeof(p));
-  p.n_img = N; p.B = B; p.L = Lsteps; p.V1 = d->V1; p.ldv = tf.V1p;
-  p.decoding_constraint = decoding_constraint; p.max_ppl = max_ppl;
-  p.logits = L.logits; p.cand_val = L.bm_cand_val; p.cand_idx = L.bm_cand_idx;
-  p.beam_seq_hist[0] = L.bm_seq[0]; p.beam_seq_hist[1] = L.bm_seq[1]; p.beam_lp_hist[0] = L.bm_lp[0]; p.beam_lp_hist[1] = L.bm_lp[1];
-  p.beam_sum = L.bm_sum; p.parent = L.bm_parent; p.it = L.it;
-  p.done_count = L.bm_done_count; p.done_p = L.bm_done_p; p.done_seq = L.bm_done_seq; p.done_lp = L.bm_done_lp;
+  UIC_TRY(beam_begin(L.beam, L.logits, tf.V1p, L.smp.it, N, B, T, d->V1, Lsteps, decoding_constraint, max_ppl, p, s));
   int cur = 0;
   UIC_TRY(tf.step(rows, 0, L.cache[cur], kmask_rows, B));              // get_logprobs_state(<bos>) (:466)
   const long long crow = (long long)d->layers * T * 3 * tf.dm;
-  for (int t = 0; t < Lsteps; ++t) {
-    p.t = t;
-    UIC_TRY(uic_beam_step_launch(p, s));
-    if (t + 1 == Lsteps) break;
+  auto advance = [&](int t_next) -> int {
     // state = [ys]: the surviving parents' histories (CaptionModel.py:90-92) -- here their cached q | k | v rows
-    UIC_TRY(uic_beam_gather_launch(d->dtype, L.bm_parent, rows, B, (int)crow, L.cache[cur], L.cache[cur ^ 1], nullptr, nullptr, nullptr, nullptr,
+    UIC_TRY(uic_beam_gather_launch(d->dtype, p.parent, rows, B, (int)crow, L.cache[cur], L.cache[cur ^ 1], nullptr, nullptr, nullptr, nullptr,
                                    nullptr, nullptr, s));
     cur ^= 1;
-    UIC_TRY(tf.step(rows, t + 1, L.cache[cur], kmask_rows, B));
-  }
-  return uic_beam_final_launch(p, seq, seq_logp, s);
+    return tf.step(rows, t_next, L.cache[cur], kmask_rows, B);
+  };
+  return beam_search(p, Lsteps, advance, s, seq, seq_logp);
 }
 
 int uic_transformer_beam_done_lists(const uic_transformer_dims* d, void* workspace, int32_t Lsteps, int32_t beam_size, int32_t* done_count,
@@ -700,11 +665,7 @@ int uic_transformer_beam_done_lists(const uic_transformer_dims* d, void* workspa
   UIC_REQUIRE(beam_size >= 1 && beam_size == d->beam && Lsteps >= 1 && Lsteps <= d->T, "transformer_beam_done_lists: bad sizes");
   hipStream_t s = (hipStream_t)stream;
   const TfLayout L = tf_layout(*d, workspace);
-  const size_t n_img = (size_t)d->N, LB = (size_t)Lsteps * beam_size;
-  UIC_TRY(uic_copy_launch(done_count, L.bm_done_count, n_img * 4, s));
-  UIC_TRY(uic_copy_launch(done_p, L.bm_done_p, n_img * LB * 4, s));
-  UIC_TRY(uic_copy_launch(done_seq, L.bm_done_seq, n_img * LB * Lsteps * 8, s));
-  return uic_copy_launch(done_lp, L.bm_done_lp, n_img * LB * Lsteps * 4, s);
+  return beam_done_lists(L.beam, d->N, Lsteps, beam_size, done_count, done_p, done_seq, done_lp, s);
 }
 
 }  // extern "C"

@@ -75,20 +75,15 @@ class AttEnsemble(AttModel):
     def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
         """AttEnsemble.py:69-98 + beam_search :100-244 with group_size = 1: all images in one device pass; `done_beams` as in
         AttModel (built on first access from the raw lists in member 0's workspace)."""
-        beam_size = opt.get('beam_size', 10)
-        group_size = opt.get('group_size', 1)
-        if group_size > 1:      # as AttModel._sample_beam: the caller only ever receives the best beam of group 0
-            beam_size = beam_size // group_size
+        beam_size = self._effective_beam_size(opt)
         self._require_eval("_sample_beam")
         assert beam_size <= self.vocab_size + 1
         fc, atts, am = self._features(fc_feats, att_feats, att_masks)
         with torch.no_grad():
             engines, params = self._members()
-            seq, lp, (cnt, dp, dseq, dlp) = TE.ensemble_sample_beam(engines, params, fc, atts, am, self.seq_length, beam_size,
-                                                                    opt.get('decoding_constraint', 0), opt.get('max_ppl', 0),
-                                                                    done_lists=True)
-        self._done_raw = (cnt, dp, dseq, dlp, beam_size)
-        self._done_beams = None
+            seq, lp, lists = TE.ensemble_sample_beam(engines, params, fc, atts, am, self.seq_length, beam_size,
+                                                     opt.get('decoding_constraint', 0), opt.get('max_ppl', 0), done_lists=True)
+        self._set_done_raw(*lists, beam_size)
         return seq, lp
 
     def _sample(self, fc_feats, attri_feats, att_feats, att_masks=None, opt={}):

@@ -313,13 +313,8 @@ class AttModel(CaptionModel):
     def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
         """AttModel._sample_beam (P/models/AttModel.py:167-196) over CaptionModel.beam_search (P/models/CaptionModel.py:
         33-177): all images in one device pass.  `self.done_beams[k]` is the reference's list for image k: its finished
-        beams sorted by -p (stable), the first beam_size of them, each {'seq', 'logps', 'unaug_p', 'p'} (:147-161,174-176)."""
-        beam_size = opt.get('beam_size', 10)
-        group_size = opt.get('group_size', 1)
-        if group_size > 1:
-            # diverse groups (CaptionModel.py:100-177): the caller only ever receives done_beams[k][0] (AttModel.py:193-194),
-            # the best beam of group 0, which never sees a diversity penalty -- a plain search over its bdash beams
-            beam_size = beam_size // group_size
+        beams sorted by -p (stable), the first beam_size of them (CaptionModel.done_beams)."""
+        beam_size = self._effective_beam_size(opt)
         if self.training:
             raise NotImplementedError("beam search runs in eval mode (eval_utils.eval_split calls model.eval() first)")
         assert beam_size <= self.vocab_size + 1
@@ -328,29 +323,10 @@ class AttModel(CaptionModel):
         am = att_masks.contiguous().float() if att_masks is not None else None
         with torch.no_grad():
             pd = {k: v.detach() for k, v in self.param_dict().items()}
-            seq, lp, (cnt, dp, dseq, dlp) = self.engine.sample_beam(pd, fc, att, am, self.seq_length, beam_size,
-                                                                   opt.get('decoding_constraint', 0), opt.get('max_ppl', 0), done_lists=True)
-        # the per-image lists are built on first access to `self.done_beams` (one D2H copy per array then): a caller that only wants
-        # the best captions -- eval_split without `verbose_beam`, the pivot decode -- pays nothing for them
-        self._done_raw = (cnt, dp, dseq, dlp, beam_size)
-        self._done_beams = None
+            seq, lp, lists = self.engine.sample_beam(pd, fc, att, am, self.seq_length, beam_size, opt.get('decoding_constraint', 0),
+                                                     opt.get('max_ppl', 0), done_lists=True)
+        self._set_done_raw(*lists, beam_size)
         return seq, lp
-
-    @property
-    def done_beams(self):
-        if getattr(self, '_done_beams', None) is None and getattr(self, '_done_raw', None) is not None:
-            cnt, dp, dseq, dlp, beam_size = self._done_raw
-            cnt_h, dp_h, unaug = cnt.cpu().tolist(), dp.cpu(), dlp.sum(-1).cpu()
-            out = []
-            for k in range(len(cnt_h)):
-                order = sorted(range(cnt_h[k]), key=lambda i: -float(dp_h[k, i]))[:beam_size]     # sorted() is stable, like the reference's
-                out.append([{'seq': dseq[k, i], 'logps': dlp[k, i], 'unaug_p': float(unaug[k, i]), 'p': float(dp_h[k, i])} for i in order])
-            self._done_beams = out
-        return getattr(self, '_done_beams', None)
-
-    @done_beams.setter
-    def done_beams(self, value):
-        self._done_beams, self._done_raw = value, None
 
     def _sample(self, fc_feats, attri_feats, att_feats, att_masks=None, opt={}):
         sample_max = opt.get('sample_max', 1)
@@ -454,7 +430,6 @@ class AdaAttModel(AttModel):
         self.core = AdaAttCore(opt, self.use_maxout)
         self._ws = None
         self._padded = self._padded_key = None
-        self._done_beams = self._done_raw = None
 
     # ------------------------------------------------------------------ engine plumbing
     @property
@@ -588,10 +563,7 @@ class AdaAttModel(AttModel):
     def _sample_beam(self, fc_feats, att_feats, att_masks=None, opt={}):
         """AttModel._sample_beam (:167-196) over CaptionModel.beam_search, all images in one device pass; `self.done_beams[k]` is the
         reference's list for image k (built on first access)."""
-        beam_size = opt.get('beam_size', 10)
-        group_size = opt.get('group_size', 1)
-        if group_size > 1:      # (as AttModel._sample_beam above: the caller only ever receives the best beam of group 0)
-            beam_size = beam_size // group_size
+        beam_size = self._effective_beam_size(opt)
         if not 1 <= beam_size <= _lib.BEAM_MAX:
             raise NotImplementedError("beam_size=%r: the MI355X beam kernels hold 1..%d beams" % (beam_size, _lib.BEAM_MAX))
         assert beam_size <= self.vocab_size + 1
@@ -602,14 +574,9 @@ class AdaAttModel(AttModel):
             lp = torch.zeros(n_img, L, dtype=torch.float32, device=att.device)
             check(lib.uic_adaatt_sample_beam(C.byref(d), C.byref(w), ptr(fc), ptr(att), ptr(am), L, B, int(opt.get('decoding_constraint', 0)),
                                              int(opt.get('max_ppl', 0)), ptr(ws), ptr(seq), ptr(lp), stream()), "adaatt_sample_beam")
-            cnt = torch.zeros(n_img, dtype=torch.int32, device=att.device)
-            dp = torch.zeros(n_img, L * B, dtype=torch.float32, device=att.device)
-            dseq = torch.zeros(n_img, L * B, L, dtype=torch.int64, device=att.device)
-            dlp = torch.zeros(n_img, L * B, L, dtype=torch.float32, device=att.device)
-            check(lib.uic_adaatt_beam_done_lists(C.byref(d), ptr(ws), L, B, ptr(cnt), ptr(dp), ptr(dseq), ptr(dlp), stream()),
-                  "adaatt_beam_done_lists")
-        self._done_raw = (cnt, dp, dseq, dlp, B)
-        self._done_beams = None
+            lists = _lib.done_list_buffers(n_img, L, B, att.device)
+            check(lib.uic_adaatt_beam_done_lists(C.byref(d), ptr(ws), L, B, *[ptr(x) for x in lists], stream()), "adaatt_beam_done_lists")
+        self._set_done_raw(*lists, B)
         return seq, lp
 
     def _sample(self, fc_feats, attri_feats, att_feats, att_masks=None, opt={}):

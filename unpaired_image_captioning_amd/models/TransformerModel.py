@@ -164,7 +164,6 @@ class TransformerModel(CaptionModel):
         self._ws = None
         self._padded = self._padded_key = None
         self._seed_counter = int(getattr(opt, 'seed', 0) or 0) & 0x7FFFFFFF
-        self._done_beams = self._done_raw = None
 
     # ------------------------------------------------------------------ engine plumbing
     def next_seed(self):
@@ -265,13 +264,8 @@ class TransformerModel(CaptionModel):
 
     def _sample_beam(self, fc_feats, attri_feats, att_feats, att_masks=None, opt={}):
         """P/models/TransformerModel.py:444-475 over CaptionModel.beam_search, all images in one device pass.  `self.done_beams[k]`
-        is the reference's list for image k, built as models/AttModel.py builds it."""
-        beam_size = opt.get('beam_size', 10)
-        group_size = opt.get('group_size', 1)
-        if group_size > 1:
-            # diverse groups (CaptionModel.py:100-177): the caller only ever receives done_beams[k][0], the best beam of group 0, which
-            # never sees a diversity penalty -- a plain search over its bdash beams (as models/AttModel.py)
-            beam_size = beam_size // group_size
+        is the reference's list for image k (CaptionModel.done_beams)."""
+        beam_size = self._effective_beam_size(opt)
         assert beam_size <= self.vocab_size + 1
         with torch.no_grad():
             lib, d, w, dv, ws, att, am = self._prepare(att_feats, att_masks, beam=int(beam_size))
@@ -281,32 +275,11 @@ class TransformerModel(CaptionModel):
             check(lib.uic_transformer_sample_beam(C.byref(d), C.byref(w), ptr(dv), ptr(att), ptr(am), L, int(beam_size),
                                                   int(opt.get('decoding_constraint', 0)), int(opt.get('max_ppl', 0)), ptr(ws), ptr(seq), ptr(lp),
                                                   stream()), "transformer_sample_beam")
-            LB = L * int(beam_size)
-            cnt = torch.zeros(n_img, dtype=torch.int32, device=att.device)
-            dp = torch.zeros(n_img, LB, dtype=torch.float32, device=att.device)
-            dseq = torch.zeros(n_img, LB, L, dtype=torch.int64, device=att.device)
-            dlp = torch.zeros(n_img, LB, L, dtype=torch.float32, device=att.device)
-            check(lib.uic_transformer_beam_done_lists(C.byref(d), ptr(ws), L, int(beam_size), ptr(cnt), ptr(dp), ptr(dseq), ptr(dlp), stream()),
+            lists = _lib.done_list_buffers(n_img, L, int(beam_size), att.device)
+            check(lib.uic_transformer_beam_done_lists(C.byref(d), ptr(ws), L, int(beam_size), *[ptr(x) for x in lists], stream()),
                   "transformer_beam_done_lists")
-        self._done_raw = (cnt, dp, dseq, dlp, int(beam_size))
-        self._done_beams = None
+        self._set_done_raw(*lists, int(beam_size))
         return seq, lp
-
-    @property
-    def done_beams(self):
-        if self._done_beams is None and self._done_raw is not None:
-            cnt, dp, dseq, dlp, beam_size = self._done_raw
-            cnt_h, dp_h, unaug = cnt.cpu().tolist(), dp.cpu(), dlp.sum(-1).cpu()
-            out = []
-            for k in range(len(cnt_h)):
-                order = sorted(range(cnt_h[k]), key=lambda i: -float(dp_h[k, i]))[:beam_size]     # sorted() is stable, like the reference's
-                out.append([{'seq': dseq[k, i], 'logps': dlp[k, i], 'unaug_p': float(unaug[k, i]), 'p': float(dp_h[k, i])} for i in order])
-            self._done_beams = out
-        return self._done_beams
-
-    @done_beams.setter
-    def done_beams(self, value):
-        self._done_beams, self._done_raw = value, None
 
     def _sample(self, fc_feats, attri_feats, att_feats, att_masks=None, opt={}):
         """P/models/TransformerModel.py:520-576: (seq, seqLogprobs), both [N, seq_length]."""

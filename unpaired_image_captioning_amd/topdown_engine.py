@@ -362,14 +362,9 @@ class TopDownEngine(object):
                                                    int(decoding_constraint), int(max_ppl), ptr(ws.buf), ptr(seq), ptr(lp), stream()),
                   "sample_beam")
             if done_lists:
-                LB = L * beam_size
-                cnt = torch.zeros(n_img, dtype=torch.int32, device=fc.device)
-                dp = torch.zeros(n_img, LB, dtype=torch.float32, device=fc.device)
-                dseq = torch.zeros(n_img, LB, L, dtype=torch.int64, device=fc.device)
-                dlp = torch.zeros(n_img, LB, L, dtype=torch.float32, device=fc.device)
-                check(self.lib.uic_topdown_beam_done_lists(C.byref(d), ptr(ws.buf), L, int(beam_size), ptr(cnt), ptr(dp), ptr(dseq),
-                                                           ptr(dlp), stream()), "beam_done_lists")
-                lists = (cnt, dp, dseq, dlp)
+                lists = _lib.done_list_buffers(n_img, L, beam_size, fc.device)
+                check(self.lib.uic_topdown_beam_done_lists(C.byref(d), ptr(ws.buf), L, int(beam_size), *[ptr(x) for x in lists], stream()),
+                      "beam_done_lists")
         finally:
             self.release(ws)
         if done_lists:
@@ -520,14 +515,9 @@ def ensemble_sample_beam(engines, params, fc, atts, att_masks, L, beam_size, dec
         check(lib.uic_topdown_ensemble_sample_beam(e.M, e.d, e.w, e.derived, e.b, L, int(beam_size), int(decoding_constraint),
                                                    int(max_ppl), e.wsp, ptr(seq), ptr(lp), stream()), "ensemble_sample_beam")
         if done_lists:
-            LB = L * beam_size
-            cnt = torch.zeros(n_img, dtype=torch.int32, device=fc.device)
-            dp = torch.zeros(n_img, LB, dtype=torch.float32, device=fc.device)
-            dseq = torch.zeros(n_img, LB, L, dtype=torch.int64, device=fc.device)
-            dlp = torch.zeros(n_img, LB, L, dtype=torch.float32, device=fc.device)
-            check(lib.uic_topdown_beam_done_lists(C.byref(e._keep[0][0]), ptr(e.ws[0].buf), L, int(beam_size), ptr(cnt), ptr(dp),
-                                                  ptr(dseq), ptr(dlp), stream()), "beam_done_lists")
-            lists = (cnt, dp, dseq, dlp)
+            lists = _lib.done_list_buffers(n_img, L, beam_size, fc.device)
+            check(lib.uic_topdown_beam_done_lists(C.byref(e._keep[0][0]), ptr(e.ws[0].buf), L, int(beam_size), *[ptr(x) for x in lists],
+                                                  stream()), "beam_done_lists")
     if done_lists:
         return seq, lp, lists
     return seq, lp
