@@ -13,11 +13,39 @@ import os
 import numpy as np
 import torch
 
-from . import _lib, models
+from . import _lib, models, trainer_checkpoint, trainer_ship
 from ._lib import check
-from .topdown_engine import live_counts, unfinished_counts
 from .misc.optimizer import FlatArena, Optim  # noqa: F401
 from .parallel_exchange import GradientExchange
+from .trainer_disc import DiscriminatorHalf
+from .trainer_nmt import NMTHalf
+
+
+def rank_seed(seed, rank):
+    """The per-rank seed rule (captioner, NMT model, discriminator, a checkpoint loaded at a larger world size): `seed` advanced
+    by one golden-ratio stride per rank, wrapped into 31 bits."""
+    return (seed + 0x9E3779B1 * rank) & 0x7FFFFFFF
+
+
+def _validation_pass(tr, name, begin, run):
+    """What Trainer.eval and Trainer.eval_unpaired share: the rank check, the eval_kwargs and the strict-`>` best-score rule.
+    begin(): raises what the pass lacks, resets its outputs and returns its extra eval_kwargs; run(eval_kwargs) (None: the pass
+    is switched off): stores the pass's results on `tr` and returns the lang_stats the score is read from.  A module-level
+    function: callers may hand the two methods a bare namespace for `self`."""
+    if tr.exchange.world_size > 1:
+        raise NotImplementedError("Trainer.%s on %d ranks: a sharded validation pass needs collectives for the captions and "
+                                  "the losses; evaluate on one rank" % (name, tr.exchange.world_size))
+    extra = begin()
+    eval_kwargs = {'split': 'val', 'dataset': getattr(tr.opt, 'input_json', '')}
+    eval_kwargs.update(vars(tr.opt))
+    eval_kwargs.update(extra)
+    if run is None:
+        return
+    stats = run(eval_kwargs)
+    current_score = stats['CIDEr'] if getattr(tr.opt, 'language_eval', 0) == 1 else - tr.i2t_val_loss
+    if tr.best_i2t_val_score is None or current_score > tr.best_i2t_val_score:
+        tr.best_i2t_val_score = current_score
+        tr.best_flag_i2t = True
 
 
 def _steps_from_host_labels(labels_np):
@@ -95,9 +123,12 @@ class _GatheredWeights(object):
         self.events = [piece_events[i] if i is not None else None for i in ev]
 
 
-class Trainer(object):
+class Trainer(NMTHalf, DiscriminatorHalf):
     """The reference Trainer's two halves: captioner (i2t: build, XE / self-critical step, save) and, after
-    `build_nmt`, the pivot NMT teacher (P/trainer.py:56-58: each half is built only when its flag asks for it)."""
+    `build_nmt`, the pivot NMT teacher (P/trainer.py:56-58: each half is built only when its flag asks for it).
+    This file holds the captioner's steps, the exchange and the validation passes; the NMT half and the discriminator are the
+    base classes (trainer_nmt.py, trainer_disc.py), batch shipping and checkpoints the two collaborators (trainer_ship.py,
+    trainer_checkpoint.py).  Every attribute the class uses is assigned in __init__."""
 
     def __init__(self, opt, exchange=None):
         self.opt = opt
@@ -109,14 +140,16 @@ class Trainer(object):
                 raise NotImplementedError("%s: evaluation and decoding only; training is not built (i2t_train_flag=0 runs Trainer.eval)"
                                           % type(self.i2t_model).__name__)
             self.i2t_model.train(bool(self.i2t_train_flag))
-        self.nmt_model = None
+        self._init_nmt()
+        self._init_disc()
         self.i2t_train_loss = 0.0
+        self.i2t_avg_reward = None
         self.sc_flag = False
         self.exchange = exchange if exchange is not None else GradientExchange()
         shared = False
         if self.i2t_model is not None:
             self._mix_rank_into_seed(self.i2t_model, self.exchange)
-            eng = getattr(self.i2t_model, 'engine', None)
+            eng = self._engine
             shared = eng is not None and hasattr(self.exchange, 'ranks_share_a_device') and self.exchange.ranks_share_a_device()
             if shared:
                 eng.recurrence |= _lib.REC_FWD_CHAIN       # several ranks on ONE GPU: per-step launches (include/uic_hip.h)
@@ -135,15 +168,43 @@ class Trainer(object):
         # unknown method
         self.method = getattr(opt, 'i2t_optim', 'adam')
         self.weight_decay = getattr(opt, 'i2t_weight_decay', 0)
+        # optimizer and exchange state: build_optimizer fills the arena, its layout and `sharded`
         self._step = 0
         self.arena = None
+        self.arena_splits = []
+        self.piece_groups = []
+        self.sharded = False
         self.last_loss = None
+        # what one step leaves for the next: the next batch's (local mask sum, 1 / global mask sum) when this step's all-reduce
+        # carried it, and the [loss, status] pair _finish_step reads
+        self._next_den = None
+        self._guard_pair = None
+        # side streams, created on first use (a constructor that opened them would initialise HIP: _require_two_hw_queues)
+        self._comm_stream = None
+        self._baseline_stream = None
+        # test switches of the self-critical step (_sample_opt, train_self_critical)
+        self.forced_samples = None
+        self.persistent_decode = False
+        self.serial_baseline = False
+        # batches and checkpoints (trainer_ship.py, trainer_checkpoint.py); next_data: what the last prefetch fetched
+        self.next_data = None
+        self._shipper = trainer_ship.BatchShipper(opt, self.i2t_model)
+        self._checkpointer = trainer_checkpoint.Checkpointer(self)
         # validation state (P/trainer.py:36-48): the caller may restore the best scores from `infos` before the first eval
+        # (best_nmt_val_acc / best_flag_nmt: trainer_nmt.py)
         self.i2t_eval_flag = getattr(opt, 'i2t_eval_flag', 1)
         self.best_i2t_val_score = None
-        self.best_nmt_val_acc = None
         self.best_flag_i2t = False
-        self.best_flag_nmt = False
+        self.i2t_val_loss = None
+        self.predictions = []
+        self.coco_predictions = []
+        self.lang_stats = None
+        self.coco_lang_stats = None
+
+    @property
+    def _engine(self):
+        """The captioner's HIP engine, or None (no captioner, or a model without one)."""
+        return getattr(self.i2t_model, 'engine', None)
 
     @staticmethod
     def _require_two_hw_queues(opt, functional=False):
@@ -175,7 +236,7 @@ class Trainer(object):
         data parallelism every rank must start from a different seed, or all shards share their noise."""
         rank = exchange.rank if exchange is not None else 0
         if rank and hasattr(model, '_seed_counter'):
-            model._seed_counter = (model._seed_counter + 0x9E3779B1 * rank) & 0x7FFFFFFF
+            model._seed_counter = rank_seed(model._seed_counter, rank)
 
     # flat-arena order [FIRST_GRADS | LSTM_W_GRADS | rest | LATE_GRADS] = gradient groups 0 / 1 / 2 / tail of uic_topdown_grad_ready_wait
     # (include/uic_hip.h): each piece's all-reduce starts while the step is still computing the following ones
@@ -191,7 +252,7 @@ class Trainer(object):
         names = self.i2t_model.param_names
         first = [k for k in names if k.startswith(self.FIRST_GRADS)]
         early_order = bool(getattr(self.opt, 'early_grads', False))
-        eng = getattr(self.i2t_model, 'engine', None)
+        eng = self._engine
         if eng is not None:
             eng.recurrence = (eng.recurrence | _lib.REC_EARLY_GRADS) if early_order else (eng.recurrence & ~_lib.REC_EARLY_GRADS)
         lstm_w = [k for k in names if k.startswith(self.LSTM_W_GRADS_EARLY if early_order else self.LSTM_W_GRADS)]
@@ -257,80 +318,19 @@ class Trainer(object):
         else:
             self.i2t_current_lr = self.lr
 
+    # ------------------------------------------------------------------ batches (trainer_ship.py)
     def to_device(self, data, per_image=True):
-        """numpy batch dict of DataLoader.get_batch -> device tensors (P/trainer.py:147-149).
+        """numpy batch dict of DataLoader.get_batch -> device tensors (P/trainer.py:147-149): BatchShipper.to_device."""
+        return self._shipper.to_device(data, per_image)
 
-        The loader replicates every image's features seq_per_img times on the host (P/misc/dataloader/dataloader.py:
-        270-277).  With opt.seq_per_img > 1 only every seq_per_img-th feature row crosses PCIe (37.7 MB instead of
-        188.7 MB at config 2) and the replication happens on the device (uic_topdown_dims.seq_per_img); the first batch
-        is checked to really be replicated.  opt.ship_replicated_features = 1 keeps the reference's behaviour."""
-        S = int(getattr(self.opt, 'seq_per_img', 1) or 1)
-        if not per_image or getattr(self.opt, 'ship_replicated_features', 0) or not hasattr(self.i2t_model, 'use_bn'):
-            S = 1
-        out = {}
-        for k in ("fc_feats", "att_feats", "labels", "masks", "att_masks"):
-            v = data.get(k)
-            if v is None:
-                continue
-            if S > 1 and k in ("fc_feats", "att_feats", "att_masks") and isinstance(v, np.ndarray) and len(v) == len(data["labels"]):
-                if not getattr(self, '_replication_checked', False):
-                    for j in range(1, S):
-                        if not (np.asarray(v[j::S]) == np.asarray(v[::S])).all():
-                            raise ValueError("opt.seq_per_img=%d but the rows of %s are not %d-fold replicated; set "
-                                             "opt.ship_replicated_features=1 for per-caption features" % (S, k, S))
-                v = v[::S]
-            if isinstance(v, np.ndarray):
-                v = torch.from_numpy(v if v.flags.writeable else v.copy())
-            out[k] = self._ship(k, v, torch.int64 if k == "labels" else torch.float32)
-        self._replication_checked = True
-        if getattr(self.opt, 'live_positions', 1) and data.get("masks") is not None and not torch.is_tensor(data["masks"]):
-            # how many positions of each decode step lie in front of their caption's end is known here, on the host, where the
-            # loader made the masks: the step's logit layer and criterion skip the others (uic_topdown_batch.live_count: the step
-            # compacts the device masks itself, nothing more is shipped; opt.live_positions = 0 computes every position)
-            out["live_count"] = live_counts(data["masks"])
-            out["unfinished_count"] = unfinished_counts(data["masks"])
-        return out
+    attach_live = staticmethod(trainer_ship.attach_live)
 
-    @staticmethod
-    def attach_live(batch):
-        """Adds the per-step counts of unmasked positions to a DEVICE batch (a resident benchmark batch; Trainer.to_device does it
-        for host batches).  One device-to-host read of the masks: call it once per batch, outside a timed region."""
-        batch["live_count"] = live_counts(batch["masks"])
-        batch["unfinished_count"] = unfinished_counts(batch["masks"])     # (rows per step the BPTT loop's d x GEMMs run over)
-        return batch
-
-    def _ship(self, key, t, dtype):
-        """Host tensor (any strides / dtype) -> device: ONE threaded gather-and-convert pass into a pinned staging buffer
-        (two per key, guarded by events) and an asynchronous copy, instead of ascontiguousarray + a pageable hipMemcpy
-        that stages a second time."""
-        if t.is_cuda:
-            return t.to(dtype)
-        ring = self.__dict__.setdefault('_pin', {}).setdefault(key, [])
-        slot = self.__dict__.setdefault('_pin_slot', {})
-        i = slot.get(key, 0)
-        slot[key] = (i + 1) % 2
-        while len(ring) <= i:
-            ring.append(None)
-        if ring[i] is None or ring[i][0].shape != t.shape or ring[i][0].dtype != dtype:
-            ring[i] = [torch.empty(t.shape, dtype=dtype, pin_memory=True), None]
-        pin, ev = ring[i]
-        if ev is not None:
-            ev.synchronize()                       # the copy that last read this buffer has finished
-        # at most 8 copy threads: a machine-wide OpenMP team (256 threads on the MI355X hosts) keeps spinning after the
-        # copy and slows the following kernel enqueues 4x (measured: the replay + BPTT enqueue 4.2 -> 16.7 ms)
-        nthr = torch.get_num_threads()
-        if nthr > 8:
-            torch.set_num_threads(8)
-        try:
-            pin.copy_(t)
-        finally:
-            if nthr > 8:
-                torch.set_num_threads(nthr)
-        dev = pin.cuda(non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        ring[i][1] = ev
-        return dev
+    def prefetch(self, data, per_image=True):
+        """Ship a batch -- or what a callable returns -- to the device on a copy stream NOW, to be consumed by the next
+        train(data) / train_self_critical(data) call with this very dict; it is left in self.next_data.  Called by
+        train(..., next_data=...) right after a step is enqueued, so the host gather and the PCIe transfer of batch k+1 run
+        while the GPU computes batch k (BatchShipper.prefetch)."""
+        self._shipper.prefetch(data, per_image, self)
 
     def train_device_batch(self, batch, t_run, den_local, next_den_local=None):
         """The timed hot path: everything from device-resident inputs to updated weights.  next_den_local (data parallel): the
@@ -339,7 +339,7 @@ class Trainer(object):
         if self.arena is None:
             self.build_optimizer()
         dev = batch["fc_feats"].device
-        if getattr(self, 'sharded', False):
+        if self.sharded:
             a = self.arena
             inv_den = self._take_next_inv_den(den_local)
             if inv_den is None:
@@ -358,14 +358,14 @@ class Trainer(object):
     def _exchange_and_adam(self, loss, grad_scale, next_den_local=None):
         """Gradient exchange + optimizer step behind a backward pass of the captioner (the XE step and the self-critical step's
         resumed backward both end in uic_topdown_xe_train_step, whose gradient-group events the overlapped forms wait on)."""
-        if getattr(self, 'sharded', False):
+        if self.sharded:
             return self._sharded_update(loss, grad_scale, next_den_local)
         if self.exchange.world_size > 1:
             # opt.allreduce_exchange: round 5's exchange -- the arena all-reduced in four pieces, the first three on the communication
             # stream as they become final; Adam on the whole arena on every rank
             lib = _lib.load()
             self.exchange.allreduce_sum_overlapped(
-                self.arena.grad, getattr(self, 'arena_splits', []) if hasattr(self.i2t_model, 'use_bn') else [],
+                self.arena.grad, self.arena_splits if hasattr(self.i2t_model, 'use_bn') else [],
                 lambda raw, g: check(lib.uic_topdown_grad_ready_wait(raw, g), "grad_ready_wait"))
         return self._guarded_adam(loss, grad_scale)
 
@@ -373,14 +373,14 @@ class Trainer(object):
     def _take_next_inv_den(self, den_local):
         """1 / (global mask sum) of THIS batch if the previous step's all-reduce carried it (its local share must be the value
         announced then), else None."""
-        nd = getattr(self, '_next_den', None)
+        nd = self._next_den
         self._next_den = None
         if nd is not None and den_local is not None and abs(float(nd[0]) - float(den_local)) <= 1e-6 * max(1.0, abs(float(den_local))):
             return nd[1]
         return None
 
     def _comm(self, dev):
-        if getattr(self, '_comm_stream', None) is None or self._comm_stream.device != dev:
+        if self._comm_stream is None or self._comm_stream.device != dev:
             self._comm_stream = torch.cuda.Stream(device=dev)
         return self._comm_stream
 
@@ -398,12 +398,12 @@ class Trainer(object):
         # scalar slots: [0] loss, [1] status flag, [2] (clip norm, unused here), [3] the next batch's mask sum
         if loss.data_ptr() != sc.data_ptr():
             sc[0:1].copy_(loss.detach().reshape(1))
-        if getattr(self.i2t_model, 'engine', None) is not None:
+        if self._engine is not None:
             sc[1:2].copy_(_lib.status_words(dev)[0:1])             # (int32 -> float: non-zero stays non-zero)
         else:
             sc[1:2].zero_()
         if next_den_local is not None:
-            sc[3:4].copy_(self._host_float(float(next_den_local), dev), non_blocking=True)
+            sc[3:4].copy_(self._shipper.host_float(float(next_den_local), dev), non_blocking=True)
         groups = self.piece_groups
 
         def wait_piece(raw, i):
@@ -415,7 +415,7 @@ class Trainer(object):
         # the logit layer's piece -- a quarter of the bytes, final when the BPTT loop STARTS -- is reduce-scattered, updated and
         # all-gathered on the communication stream while the loop runs (no kernel of the step reads logit.weight after that point);
         # the status word it is guarded by is final then too (the step's only persistent launch is the forward recurrence)
-        has_eng = getattr(self.i2t_model, 'engine', None) is not None
+        has_eng = self._engine is not None
         pipe = (0,) if (has_eng and overlap and groups and groups[0] == 0 and not getattr(self.opt, 'no_pipelined_logit_piece', 0)) else ()
         # opt.bf16_gradient_exchange: every piece that is NOT pipelined behind the BPTT loop -- i.e. the bytes that are still on the
         # wire when the step has joined -- is reduce-scattered as bf16
@@ -427,20 +427,10 @@ class Trainer(object):
         self._guard_pair = pair
         if next_den_local is not None:
             self._next_den = (float(next_den_local), sc[3:4].reciprocal())
-        eng = getattr(self.i2t_model, 'engine', None)
+        eng = self._engine
         if eng is not None and getattr(eng, 'gathered', None) is not None:
             eng.gathered.set_events(events)
         return pair[0]
-
-    def _host_float(self, x, dev):
-        """A host float as a 1-element device tensor without a synchronous pageable copy (ring of pinned floats)."""
-        if getattr(self, '_pinf', None) is None:
-            self._pinf = torch.zeros(64, dtype=torch.float32).pin_memory()
-            self._pinf_i = 0
-        i = self._pinf_i
-        self._pinf_i = (i + 1) % 64
-        self._pinf[i] = x
-        return self._pinf[i:i + 1].to(dev, non_blocking=True)
 
     def gather_masters(self):
         """Collective (every rank calls it): after a sharded bf16 step a rank's f32 master weights are current only inside its own
@@ -460,7 +450,7 @@ class Trainer(object):
         scalar."""
         a = self.arena
         self._step += 1
-        has_eng = getattr(self.i2t_model, 'engine', None) is not None
+        has_eng = self._engine is not None
         status = _lib.status_words(a.flat.device) if has_eng else None
         self._guard_pair = None
         if self.exchange.world_size > 1:
@@ -477,16 +467,39 @@ class Trainer(object):
     def _raise_if_timed_out(self, cause):
         """After a failure inside a step: if a persistent launch of the step timed out, clear the status word and raise
         PersistentTimeout (chained to `cause`) -- the step's update never ran or was skipped on the device."""
-        if isinstance(cause, _lib.PersistentTimeout) or getattr(self.i2t_model, 'engine', None) is None or self.arena is None:
+        if isinstance(cause, _lib.PersistentTimeout) or self._engine is None or self.arena is None:
             return
         word = _lib.status_words(self.arena.flat.device)
         try:
             code = int(word[0].item())
         except Exception:
             return
-        if code != 0:
-            word[0:1].zero_()
-            raise _lib.PersistentTimeout("persistent recurrence kernel timed out (code 0x%x): the step failed before its update" % code) from cause
+        if code != 0:                                           # (no counter to take back: the caller failed before or inside the update)
+            self._roll_back(self.arena.flat.device, None, (), _lib.PersistentTimeout(
+                "persistent recurrence kernel timed out (code 0x%x): the step failed before its update" % code), cause)
+
+    def _reset_step_carry(self):
+        """What one step leaves behind for the next and a checkpoint does not hold (Checkpointer.load): the gather events, the
+        carried next-batch denominator, a prefetched batch, the pair _finish_step would read."""
+        gw = getattr(self._engine, 'gathered', None)
+        if gw is not None:
+            gw.events = [None] * 4               # (the operand copy was rebuilt on this stream: nothing to wait for)
+        self._next_den = None
+        self._shipper.drop_prefetched()
+        self._guard_pair = None
+
+    def _roll_back(self, dev, owner, counters, error, cause=None):
+        """THE roll-back after a timed-out persistent launch, whose update the device skipped: clear the status word on `dev`
+        (None: no engine, no word), take the step counters `counters` of `owner` back by one -- the skipped step does not count
+        for Adam's bias correction --, raise `error` (chained to `cause` if given).  The captioner's steps pass their _step, the
+        NMT step (trainer_nmt.py) Optim's two counters."""
+        if dev is not None:
+            _lib.status_words(dev)[0:1].zero_()
+        for name in counters:
+            setattr(owner, name, getattr(owner, name) - 1)
+        if cause is not None:
+            raise error from cause
+        raise error
 
     def _finish_step(self, loss):
         """The step's ONE host sync (the reference's loss.item(), P/trainer.py:172): returns the loss as a float and raises --
@@ -494,7 +507,7 @@ class Trainer(object):
         long kernel on another stream).  The update was then already skipped on the device (_guarded_adam): weights, moments
         and the step counter are those of before the step, and training can go on after the caller has dealt with the cause
         (engine.recurrence |= _lib.REC_FWD_CHAIN selects per-step launches, which cannot time out)."""
-        pair = getattr(self, '_guard_pair', None)
+        pair = self._guard_pair
         self._guard_pair = None
         try:
             if pair is not None:
@@ -505,48 +518,13 @@ class Trainer(object):
                 _lib.persistent_status(self.arena.flat.device)  # (clears nothing: the local word is zero too)
                 return vals[0]
             val = loss.item()
-            if getattr(self.i2t_model, 'engine', None) is not None:
+            if self._engine is not None:
                 _lib.persistent_status(self.arena.flat.device)  # raises and clears the word if the launch timed out
             return val
-        except _lib.PersistentTimeout:
+        except _lib.PersistentTimeout as e:
             # ONLY the time-out rolls the step back (the update was skipped on the device): any other failure -- a HIP error out
             # of loss.item(), a collective's -- leaves the counters and the launch statistics alone
-            if getattr(self.i2t_model, 'engine', None) is not None:
-                _lib.status_words(self.arena.flat.device)[0:1].zero_()
-            self._step -= 1                                     # the skipped step does not count for Adam's bias correction
-            raise
-
-    def prefetch(self, data, per_image=True):
-        """Ship a batch to the device on a copy stream NOW (pinned staging + asynchronous H2D), to be consumed by the next
-        train(data) / train_self_critical(data) call with this very dict.  Called by train(..., next_data=...) right after a
-        step is enqueued, so the host gather and the PCIe transfer of batch k+1 run while the GPU computes batch k."""
-        if getattr(self, '_copy_stream', None) is None:
-            self._copy_stream = torch.cuda.Stream()
-        with torch.cuda.stream(self._copy_stream):
-            if callable(data):
-                # e.g. `lambda: loader.get_batch('train')`: the loader's host work, its H2D copies and its assembly kernel
-                # all happen here -- after this step was enqueued, on the copy stream; the batch is left in self.next_data
-                data = data()
-            self.next_data = data
-            if data is None:                          # the caller's source is exhausted
-                self._prefetched = None
-                return
-            batch = self.to_device(data, per_image)
-            ev = torch.cuda.Event()
-            ev.record()
-        self._prefetched = (id(data), per_image, batch, ev)
-
-    def _device_batch(self, data, per_image=True):
-        pf = getattr(self, '_prefetched', None)
-        self._prefetched = None
-        if pf is not None and pf[0] == id(data) and pf[1] == per_image:
-            cur = torch.cuda.current_stream()
-            cur.wait_event(pf[3])
-            for t in pf[2].values():
-                if torch.is_tensor(t):
-                    t.record_stream(cur)               # allocated on the copy stream, consumed on this one
-            return pf[2]
-        return self.to_device(data, per_image)
+            self._roll_back(self.arena.flat.device if self._engine is not None else None, self, ('_step',), e)
 
     def train(self, data, loader=None, iteration=None, epoch=None, nmt_epoch=None, next_data=None):
         """Trainer.train for the XE captioner step (P/trainer.py:141-173,193).  next_data (optional extension): the
@@ -556,14 +534,14 @@ class Trainer(object):
         t_run = _steps_from_host_labels(labels_np)
         T = labels_np.shape[1] - 1
         den_local = self._mask_sum(data)
-        batch = self._device_batch(data)
-        if getattr(self, 'sharded', False) or (self.arena is None and self.exchange.world_size > 1):
+        batch = self._shipper.device_batch(data)
+        if self.sharded or (self.arena is None and self.exchange.world_size > 1):
             # sharded exchange: the NEXT batch's mask sum rides in this step's small all-reduce, so that no collective sits in
             # front of the next forward pass.  A dict is known now; a callable is fetched after the step's compute is enqueued (its
             # host work then overlaps the GPU's), and the exchange -- which needs the number -- is enqueued behind it
             if self.arena is None:
                 self.build_optimizer()
-        if getattr(self, 'sharded', False) and next_data is not None:
+        if self.sharded and next_data is not None:
             if callable(next_data):
                 a = self.arena
                 inv_den = self._take_next_inv_den(den_local)
@@ -594,7 +572,7 @@ class Trainer(object):
         """Options of the self-critical step's sampling pass (P/trainer.py:167: sample_max = 0).  self.forced_samples (tests):
         an int64 [rows, L] tensor the pass replays instead of drawing -- its log-probs and gradients are those of these tokens."""
         o = {'sample_max': 0, 'captions_per_image': S}
-        forced = getattr(self, 'forced_samples', None)
+        forced = self.forced_samples
         if forced is not None:
             o['forced_tokens'] = forced
         return o
@@ -603,7 +581,7 @@ class Trainer(object):
         """The sampling pass (train mode) and the greedy baseline (eval mode, P/misc/rewards.py:42-47) of the self-critical
         step; overlap: the baseline on a second stream beside the sampling pass."""
         if overlap:
-            if getattr(self, '_baseline_stream', None) is None:
+            if self._baseline_stream is None:
                 self._baseline_stream = torch.cuda.Stream()
             # the derived weight copies are rebuilt once, here, on the current stream (hold_weights: later calls reuse them);
             # the baseline stream then orders itself behind that and behind the batch's H2D copies
@@ -652,7 +630,7 @@ class Trainer(object):
         from .misc import rewards
         if self.arena is None:
             self.build_optimizer()
-        batch = self._device_batch(data)
+        batch = self._shipper.device_batch(data)
         model = self.i2t_model
         fc, att, am = batch["fc_feats"], batch.get("att_feats"), batch.get("att_masks")
         # (a model without attention features -- the `fc` captioner -- counts its rows in fc_feats)
@@ -660,7 +638,7 @@ class Trainer(object):
         n_rows = len(data["labels"]) if data.get("labels") is not None else feat_rows
         S = n_rows // feat_rows                           # > 1 when to_device shipped every image once
         import contextlib
-        eng = getattr(model, 'engine', None)
+        eng = self._engine
         try:
             # the weights stay put until Adam below: ONE weight refresh serves the sampling pass, the greedy baseline and the replay
             with (eng.hold_weights() if hasattr(eng, 'hold_weights') else contextlib.nullcontext()):
@@ -672,9 +650,9 @@ class Trainer(object):
                 # self.persistent_decode: each pass as ONE persistent launch (rnn_persist.hip's decode mode).  A persistent launch
                 # holds every CU, so the two passes then run one after the other -- measured slower for this step than the two
                 # launch chains side by side (profiles/), hence off by default here; a lone decode pass (eval) takes it by itself.
-                persistent = bool(getattr(self, 'persistent_decode', False))
+                persistent = bool(self.persistent_decode)
                 overlap = hasattr(eng, 'hold_weights') and int(getattr(model, 'use_bn', 0) or 0) == 0 and \
-                    not getattr(self, 'serial_baseline', False) and not persistent
+                    not self.serial_baseline and not persistent
                 rec0 = getattr(eng, 'recurrence', 0)
                 if eng is not None and not persistent:
                     eng.recurrence = rec0 | _lib.REC_FWD_CHAIN
@@ -697,7 +675,7 @@ class Trainer(object):
                     reward = np.asarray(reward_fn(data, gen_result.cpu().numpy(), greedy_res.cpu().numpy()), dtype=np.float32)
                     reward_t = torch.from_numpy(reward).cuda()
                 dw = float(getattr(self.opt, 'disc_reward_weight', 0) or 0)
-                if dw > 0 and getattr(self, 'discriminator', None) is not None:
+                if dw > 0 and self.discriminator is not None:
                     # adversarial reward of BASELINE configs[3]: + w (D(sampled) - D(greedy)), the same self-critical form, per row
                     g_rows = greedy_res.repeat_interleave(S, 0) if greedy_res.shape[0] != gen_result.shape[0] else greedy_res
                     adv = self.discriminator_scores(gen_result) - self.discriminator_scores(g_rows)
@@ -744,128 +722,6 @@ class Trainer(object):
         self.i2t_avg_reward = float(avg.item())
         return self.i2t_train_loss
 
-    # ------------------------------------------------------------------ sentence discriminator (BASELINE configs[3]; parity unpinned)
-    def build_discriminator(self):
-        """The CNN sentence discriminator of the unpaired / adversarial configuration (models/Discriminator.py) with its own flat
-        Adam arena; data parallel like the captioner (gradient arena summed over the ranks)."""
-        from .models import SentenceDiscriminator
-        from .misc.optimizer import FlatArena
-        self.discriminator = SentenceDiscriminator(self.opt).cuda()
-        rank = self.exchange.rank if self.exchange is not None else 0
-        self.discriminator.seed = (self.discriminator.seed + 0x9E3779B1 * rank) & 0x7FFFFFFF    # per-rank dropout noise
-        ex = self.exchange
-        self.disc_sharded = bool(ex is not None and ex.world_size > 1 and not getattr(self.opt, 'allreduce_exchange', 0))
-        if self.disc_sharded:        # one piece, f32 masters gathered in place (the discriminator's kernels read the masters)
-            names = [k for k, _ in self.discriminator.named_parameters()]
-            self.disc_arena = FlatArena(self.discriminator, names, world=ex.world_size, rank=ex.rank, pieces=[names])
-        else:
-            self.disc_arena = FlatArena(self.discriminator)
-        self.disc_lr = float(getattr(self.opt, 'disc_learning_rate', 1e-4) or 1e-4)
-        self._disc_step = 0
-        return self.discriminator
-
-    def _pad_rows(self, seq):
-        """Caption rows [N, L'] (int64, 0 = end) as the discriminator's [N, seq_length] rows."""
-        L = self.discriminator.L
-        seq = seq.cuda() if not seq.is_cuda else seq
-        if seq.shape[1] < L:
-            seq = torch.cat([seq, seq.new_zeros(seq.shape[0], L - seq.shape[1])], 1)
-        return seq[:, :L].contiguous().long()
-
-    def discriminator_scores(self, seq):
-        self.discriminator.eval()
-        return self.discriminator.scores(self._pad_rows(seq))
-
-    def train_discriminator(self, real_seq, fake_seq):
-        """One BCE step: real caption rows (label 1) against generated rows (label 0).  Returns the loss (one host sync)."""
-        if getattr(self, 'discriminator', None) is None:
-            self.build_discriminator()
-        D, a = self.discriminator, self.disc_arena
-        D.train()
-        tok = torch.cat([self._pad_rows(real_seq), self._pad_rows(fake_seq)])
-        lab = torch.cat([torch.ones(real_seq.shape[0]), torch.zeros(fake_seq.shape[0])]).cuda()
-        a.zero_grad()
-        loss = D.bce(D(tok), lab)
-        loss.backward()
-        self._disc_step += 1
-        if getattr(self, 'disc_sharded', False):
-            a.scalars[0:2].zero_()
-            a.scalars[0:1].copy_(loss.detach().reshape(1))
-            pair, _ = a.sharded_step(self.exchange, self.disc_lr, self.betas, self.eps, self._disc_step, 1.0 / self.exchange.world_size)
-            self.disc_train_loss = float(pair[0].item()) / self.exchange.world_size      # (mean of the ranks' batch means)
-            return self.disc_train_loss
-        self.exchange.allreduce_sum(a.grad)
-        a.adam(self.disc_lr, self.betas, self.eps, self._disc_step, grad_scale=1.0 / self.exchange.world_size)
-        self.disc_train_loss = loss.item()
-        return self.disc_train_loss
-
-    # ------------------------------------------------------------------ pivot NMT half (P/trainer.py:80-94,175-193)
-    def build_nmt(self, src_dict, tgt_dict):
-        """Trainer.build_nmt: encoder/decoder/NMTModel, the generator attached as `model.generator`, NMT_loss, and the
-        optimizer over the model's flat arena.  `src_dict` / `tgt_dict`: onmt.Dict-like (`.size()`) or plain sizes."""
-        import torch.nn as nn
-        from .models import NMT_Models
-        from .misc import criterion
-        opt = self.opt
-        tgt_size = int(tgt_dict.size()) if hasattr(tgt_dict, 'size') else int(tgt_dict)
-        self.nmt_encoder = NMT_Models.Encoder(opt, src_dict)
-        self.nmt_decoder = NMT_Models.Decoder(opt, tgt_dict)
-        self.nmt_model = NMT_Models.NMTModel(opt, self.nmt_encoder, self.nmt_decoder, src_dict, tgt_dict, False)
-        self._mix_rank_into_seed(self.nmt_model, self.exchange)
-        self.nmt_generator = nn.Sequential(nn.Linear(opt.rnn_size, tgt_size), nn.LogSoftmax(dim=-1))
-        param_init = getattr(opt, 'param_init', 0.1)
-        if param_init:
-            for p in list(self.nmt_model.parameters()) + list(self.nmt_generator.parameters()):
-                p.data.uniform_(-param_init, param_init)
-        self.nmt_model.generator = self.nmt_generator
-        self.dp_nmt_model = self.nmt_model
-        self.nmt_model.cuda()
-        self.nmt_model.train(bool(getattr(opt, 'nmt_train_flag', 1)))
-        self.nmt_loss = criterion.NMTCriterion(tgt_size, opt)
-        self.nmt_crit = criterion.NMT_loss(opt, self.nmt_generator, self.nmt_loss)
-        self.optim = Optim(opt, self.exchange)
-        self.optim.set_parameters(None, self.nmt_model)
-        self.nmt_train_ppl = self.nmt_train_acc = 0.0
-        return self.nmt_model
-
-    def train_nmt(self, nmt_batch, loader=None, nmt_epoch=None, update_lr=False):
-        """The NMT branch of Trainer.train (P/trainer.py:175-193): zero_grad, forward, NMT_loss, backward,
-        Optim.step (noam LR, clip_grad_norm, Adam).  Returns the summed NLL of the batch (host float)."""
-        if update_lr:
-            self.optim.update_LearningRate('nmt', nmt_epoch)
-        self.optim.zero_grad(nmt_direct=True)         # (no 360 MB fill: the in-place backward below overwrites every gradient)
-        self.nmt_model.unit_loss_gradient = True      # loss.backward() below: the kernels may write the gradient arena in place
-        outputs, attn, dec_state, upper_bounds = self.dp_nmt_model(nmt_batch.src, nmt_batch.tgt, nmt_batch.lengths, None)
-        nmt_loss = self.nmt_crit(loader, nmt_batch, outputs, attn)
-        nmt_loss.backward()
-        sharded = getattr(self.optim, 'nmt_sharded', False)
-        if sharded:
-            # the step's loss rides in the sharded exchange's small all-reduce (slot 0 of the arena's scalar slots)
-            self.optim.nmt_arena.scalars[0:1].copy_(nmt_loss.detach().reshape(1))
-        self.optim.step()
-        # the statistics are read AFTER the whole step is enqueued (one host sync per step, at its end)
-        self.nmt_crit.report_stats.n_src_words += int(nmt_batch.lengths.sum())
-        self.nmt_train_ppl = self.nmt_crit.report_stats.ppl()
-        self.nmt_train_acc = self.nmt_crit.report_stats.accuracy()
-        loss_d = nmt_loss.detach()
-        if sharded:
-            loss_d = self.optim.last_pair[0]
-        elif self.exchange is not None and self.exchange.world_size > 1:
-            # the criterion is a SUM over target words (size_average=False, P/misc/criterion.py:126-136): the whole batch's loss
-            # is the sum over the ranks' column shards, as DataParallel(dim=1) + gather gives the reference (P/trainer.py:88,178)
-            loss_d = loss_d.float().reshape(1).clone()
-            self.exchange._sum(loss_d)
-        val = float(loss_d)                           # (the step's host sync)
-        guard = getattr(self.optim, 'last_guard', None)
-        if guard is not None and float(guard[0].item()) != 0:
-            # a persistent launch of this step timed out (on some rank): Optim.step skipped the update on the device
-            _lib.status_words(self.optim.nmt_arena.flat.device)[0:1].zero_()
-            self.optim._step -= 1
-            self.optim._nmt_steps -= 1
-            raise _lib.PersistentTimeout("persistent NMT kernel timed out: this step's update was skipped (weights and moments unchanged); "
-                                         "engine.recurrence |= _lib.REC_FWD_CHAIN selects per-step launches")
-        return val
-
     # ------------------------------------------------------------------ validation (P/trainer.py:195-215)
     def eval(self, loader, coco_loader=None):
         """Trainer.eval, captioner half: eval_utils.eval_split over the 'val' split -- teacher-forced loss, one decoded caption per
@@ -874,31 +730,17 @@ class Trainer(object):
         best_i2t_val_score and best_flag_i2t; the caller saves with save_models('-best' if the flag is set else '') and clears
         the flag.  The NMT half is eval_nmt."""
         from . import eval_utils
-        if self.exchange.world_size > 1:
-            raise NotImplementedError("Trainer.eval on %d ranks: a sharded validation pass needs collectives for the captions and "
-                                      "the losses; evaluate on one rank" % self.exchange.world_size)
-        self.predictions = []
-        eval_kwargs = {'split': 'val', 'dataset': getattr(self.opt, 'input_json', '')}
-        eval_kwargs.update(vars(self.opt))
-        if self.i2t_eval_flag:
+
+        def begin():
+            self.predictions = []
+            return {}
+
+        def run(eval_kwargs):
             eval_tmp = eval_utils.eval_split(self.opt, loader, self.dp_i2t_model, None, eval_kwargs)
             self.i2t_val_loss, self.predictions, self.lang_stats, _, _ = eval_tmp
             self.coco_lang_stats = self.lang_stats
-            current_score = self.lang_stats['CIDEr'] if getattr(self.opt, 'language_eval', 0) == 1 else - self.i2t_val_loss
-            if self.best_i2t_val_score is None or current_score > self.best_i2t_val_score:
-                self.best_i2t_val_score = current_score
-                self.best_flag_i2t = True
-
-    def build_pivot(self, caption_vocab, scoring_vocab, src_dict=None, tgt_dict=None, max_words=None):
-        """The bridge of the unpaired validation pass (misc/pivot.py): `caption_vocab` / `scoring_vocab` are the ix_to_word of the
-        pivot-language loader and of the COCO loader; the dictionaries default to the NMT model's.  Stored as self.pivot_bridge."""
-        from .misc import pivot
-        src_dict = self.nmt_model.src_dict if src_dict is None else src_dict
-        tgt_dict = self.nmt_model.tgt_dict if tgt_dict is None else tgt_dict
-        device = next(self.nmt_model.parameters()).device
-        self.pivot_bridge = pivot.PivotBridge(caption_vocab, src_dict, tgt_dict, scoring_vocab, device=device,
-                                              max_words=pivot.MAX_WORDS if max_words is None else max_words)
-        return self.pivot_bridge
+            return self.lang_stats
+        _validation_pass(self, 'eval', begin, run if self.i2t_eval_flag else None)
 
     def eval_unpaired(self, loader, coco_loader):
         """Trainer.eval with opt.coco_eval_flag (P/trainer.py:195-215): eval_utils.eval_split_coco_unpaired over the 'val' splits of
@@ -906,138 +748,22 @@ class Trainer(object):
         coco_lang_stats, best_i2t_val_score and best_flag_i2t: a strict `>` on coco_lang_stats['CIDEr'] (opt.language_eval == 1)
         or on -val_loss.  Needs build_nmt and build_pivot; the models' train / eval modes are restored."""
         from . import eval_utils
-        if self.exchange.world_size > 1:
-            raise NotImplementedError("Trainer.eval_unpaired on %d ranks: a sharded validation pass needs collectives for the captions "
-                                      "and the losses; evaluate on one rank" % self.exchange.world_size)
-        if getattr(self, 'pivot_bridge', None) is None:
-            raise RuntimeError("Trainer.eval_unpaired needs Trainer.build_pivot(caption_vocab, scoring_vocab) first")
-        self.predictions, self.coco_predictions = [], []
-        eval_kwargs = {'split': 'val', 'dataset': getattr(self.opt, 'input_json', '')}
-        eval_kwargs.update(vars(self.opt))
-        eval_kwargs['pivot_bridge'] = self.pivot_bridge
-        eval_tmp = eval_utils.eval_split_coco_unpaired(self.opt, loader, coco_loader, self.dp_i2t_model, self.dp_nmt_model, eval_kwargs)
-        self.i2t_val_loss, self.predictions, self.coco_predictions, self.lang_stats, self.coco_lang_stats, _, _ = eval_tmp
-        current_score = self.coco_lang_stats['CIDEr'] if getattr(self.opt, 'language_eval', 0) == 1 else - self.i2t_val_loss
-        if self.best_i2t_val_score is None or current_score > self.best_i2t_val_score:
-            self.best_i2t_val_score = current_score
-            self.best_flag_i2t = True
 
-    def eval_nmt(self, batches):
-        """The NMT half of the validation pass (P/trainer.py:212-215, P/eval_utils.py:313-317): the given validation batches
-        through dp_nmt_model in eval mode and a fresh NMT_loss, no backward pass.  Sets nmt_valid_ppl, nmt_valid_acc,
-        best_nmt_val_acc and best_flag_nmt (strict `>`)."""
-        from .misc import criterion
-        crit = criterion.NMT_loss(self.opt, self.nmt_generator, self.nmt_loss, eval=True)
-        was_training = self.nmt_model.training
-        self.nmt_model.eval()
-        try:
-            with torch.no_grad():
-                for batch in batches:
-                    outputs, attn, _, _ = self.dp_nmt_model(batch.src, batch.tgt, batch.lengths, None)
-                    crit(None, batch, outputs, attn)
-        finally:
-            self.nmt_model.train(was_training)
-        self.nmt_valid_ppl = crit.total_stats.ppl()
-        self.nmt_valid_acc = crit.total_stats.accuracy()
-        if self.best_nmt_val_acc is None or self.nmt_valid_acc > self.best_nmt_val_acc:
-            self.best_nmt_val_acc = self.nmt_valid_acc
-            self.best_flag_nmt = True
+        def begin():
+            if self.pivot_bridge is None:
+                raise RuntimeError("Trainer.eval_unpaired needs Trainer.build_pivot(caption_vocab, scoring_vocab) first")
+            self.predictions, self.coco_predictions = [], []
+            return {'pivot_bridge': self.pivot_bridge}
 
-    # ------------------------------------------------------------------ checkpoints (DESIGN.md, "Checkpoints")
-    STATE_VERSION = 1
+        def run(eval_kwargs):
+            eval_tmp = eval_utils.eval_split_coco_unpaired(self.opt, loader, coco_loader, self.dp_i2t_model, self.dp_nmt_model, eval_kwargs)
+            self.i2t_val_loss, self.predictions, self.coco_predictions, self.lang_stats, self.coco_lang_stats, _, _ = eval_tmp
+            return self.coco_lang_stats
+        _validation_pass(self, 'eval_unpaired', begin, run)
 
-    def _seed_counters_begin(self):
-        """The models' _seed_counter of every rank, collected with ONE small collective: every rank writes the 16-bit halves of
-        its counters (exact as floats) into its own slots of a zero vector, and the vector is summed on the current stream.
-        Returns (model kinds, rows): rows is a host list on one rank, else a HOST tensor [world, 2 * kinds] -- for device models a
-        pinned one that an asynchronous copy on the CURRENT stream fills, right behind the sum: the device tensor is allocated,
-        summed and read on one stream, so the allocator may hand its block on as soon as this returns.  Nobody waits here;
-        _seed_counters_end reads the rows once an event recorded behind this call has completed."""
-        ex = self.exchange
-        world, rank = ex.world_size, ex.rank
-        mods = [('i2t', self.i2t_model), ('nmt', getattr(self, 'nmt_model', None))]
-        mods = [(k, m) for k, m in mods if m is not None and hasattr(m, '_seed_counter')]
-        mine = [h for _, m in mods for h in (int(m._seed_counter) >> 16, int(m._seed_counter) & 0xFFFF)]
-        kinds = [k for k, _ in mods]
-        if world == 1 or not mods:
-            return kinds, [mine]
-        t = torch.zeros(world, len(mine), dtype=torch.float32)
-        t[rank] = torch.tensor(mine, dtype=torch.float32)
-        dev = next(mods[0][1].parameters()).device
-        if dev.type != 'cuda':
-            ex._sum(t)
-            return kinds, t
-        with torch.cuda.device(dev):
-            t = t.pin_memory().to(dev, non_blocking=True)
-            ex._sum(t)
-            rows = torch.empty(t.shape, dtype=t.dtype, pin_memory=True)
-            rows.copy_(t, non_blocking=True)
-        return kinds, rows
-
-    @staticmethod
-    def _seed_counters_end(kinds, rows):
-        if torch.is_tensor(rows):
-            rows = [[int(x) for x in row] for row in rows.tolist()]
-        return {k: [(row[2 * j] << 16) | row[2 * j + 1] for row in rows] for j, k in enumerate(kinds)}
-
-    @staticmethod
-    def _write(obj, path):
-        """torch.save to a temporary name, then os.replace: a reader never sees half a file."""
-        tmp = path + '.tmp'
-        torch.save(obj, tmp)
-        os.replace(tmp, path)
-
-    class _Snapshot(object):
-        """What one model contributes to a checkpoint, copied twice: device-to-device on the step's stream into `dev` (the step
-        goes on and changes the arena), from there to the pinned `host` buffers on the copy stream.  Rows of dev / host: the
-        arena's flat and its state arenas (FlatArena.states: two for Adam, none for sgd) up to the scalar slots.  `extra`:
-        state_dict entries that do not live in the arena -- the BatchNorm buffers -- as {key: [device copy, pinned copy]}.  All buffers are allocated once and reused by every save."""
-
-        def __init__(self, arena):
-            self.n = arena.scalars_off if arena is not None else 0
-            self.rows = 1 + len(arena.states) if arena is not None else 0
-            self.dev = self.host = None
-            if arena is not None:
-                self.dev = torch.empty(self.rows, self.n, dtype=torch.float32, device=arena.flat.device)
-                # (one host tensor per row: torch.save writes a view's WHOLE storage, and the weights and the moments go to two files)
-                self.host = [torch.empty(self.n, dtype=torch.float32, pin_memory=arena.flat.is_cuda) for _ in range(self.rows)]
-            self.extra = {}
-            self.layout = []
-
-        def take(self, model, arena):
-            """On the current stream: arena -> dev, and the layout of model.state_dict(): (key, arena offset or None, shape)."""
-            if arena is not None:
-                for row, src in enumerate([arena.flat] + arena.states):
-                    self.dev[row].copy_(src[:self.n])
-            self.layout = []
-            for k, v in model.state_dict().items():
-                v = v.detach()
-                off = arena.offsets.get(k) if arena is not None else None
-                if off is not None and v.data_ptr() != arena.flat.data_ptr() + 4 * off:
-                    off = None                                  # (a parameter that was re-homed after the arena was built)
-                if off is None:
-                    slot = self.extra.get(k)
-                    if slot is None or slot[0].shape != v.shape or slot[0].dtype != v.dtype or slot[0].device != v.device:
-                        slot = self.extra[k] = [torch.empty_like(v), torch.empty(v.shape, dtype=v.dtype, pin_memory=v.is_cuda)]
-                    slot[0].copy_(v)
-                self.layout.append((k, off, tuple(v.shape)))
-
-        def to_host(self):
-            """On the copy stream, behind the event that follows take()."""
-            if self.dev is not None:
-                for row in range(self.rows):
-                    self.host[row].copy_(self.dev[row], non_blocking=True)
-            for k, off, _ in self.layout:
-                if off is None:
-                    self.extra[k][1].copy_(self.extra[k][0], non_blocking=True)
-
-        def state_dict(self):
-            """The model's state_dict as views of the pinned buffers (once the copy stream's event has completed)."""
-            out = {}
-            for k, off, shape in self.layout:
-                n = int(np.prod(shape, dtype=np.int64))
-                out[k] = self.host[0][off:off + n].view(shape) if off is not None else self.extra[k][1]
-            return out
+    # ------------------------------------------------------------------ checkpoints (trainer_checkpoint.py; DESIGN.md, "Checkpoints")
+    STATE_VERSION = trainer_checkpoint.STATE_VERSION
+    _write = staticmethod(trainer_checkpoint.write)
 
     def save_models(self, tag=''):
         """P/trainer.py:98-104: model_i2t / model_nmt = state_dict of the un-wrapped module, optimizer_i2t / optimizer_nmt = the
@@ -1051,201 +777,13 @@ class Trainer(object):
         self.wait_for_save()
 
     def save_models_async(self, tag=''):
-        """save_models without the wait: the step's stream only copies the arenas device-to-device into a snapshot (behind the
-        step's Adam, and behind the gathers of the sharded exchange); the snapshot travels to pinned host memory on the copy
-        stream and a writer thread writes the files from there, while the following steps run.  Counters and seed counters are
-        taken now, on the host.  A save still in flight is waited for first; wait_for_save() joins the writer and re-raises
-        what it failed with.  The device-to-device copy stays on the step's stream on purpose: a kernel on a side stream beside
-        a persistent recurrence launch is what _finish_step names as a cause of PersistentTimeout."""
-        import threading
-        self.wait_for_save()
-        path = self.opt.checkpoint_path
-        ex = self.exchange
-        writer = ex is None or ex.rank == 0
-        nmt = getattr(self, 'nmt_model', None) is not None and bool(getattr(self.opt, 'nmt_train_flag', 0))
-        if self.arena is not None and getattr(self, 'sharded', False):
-            dev = self.arena.flat.device        # (the pipelined piece's Adam and the weights' all-gathers run on the communication stream)
-            torch.cuda.current_stream(dev).wait_stream(self._comm(dev))
-        self.gather_masters()        # (sharded bf16 exchange: a collective -- every rank calls save_models, as every rank runs the loop)
-        if self.arena is not None:
-            self.arena.gather_moments(ex)
-        if nmt:
-            self.optim.nmt_arena.gather_moments(self.optim.exchange)
-        kinds, rows = self._seed_counters_begin()
-        o = self.optim if nmt else None
-        on_gpu = torch.is_tensor(rows) and rows.is_pinned()
-        state = {'format_version': self.STATE_VERSION, 'world_size': ex.world_size, 'step': self._step,
-                 'i2t_current_lr': float(self.i2t_current_lr), 'sc_flag': bool(self.sc_flag),
-                 'ss_prob': float(getattr(self.i2t_model, 'ss_prob', 0.0)) if self.i2t_model is not None else 0.0,
-                 'optim': None if o is None else o.counters()}
-        # (optional keys: a file without them was written when every arena ran Adam)
-        if self.arena is not None:
-            state['i2t_optim'] = self.arena.method
-        if nmt:
-            state['nmt_optim'] = o.nmt_arena.method
-        if not writer:
-            return                   # one writer: the ranks hold identical weights
-        # (kind, model, arena, the optimizer's lr / betas / eps / step / weight decay for the optimizer file)
-        jobs = []
-        if self.i2t_model is not None:
-            jobs.append(('i2t', self.i2t_model, self.arena, (self.i2t_current_lr, self.betas, self.eps, self._step, self.weight_decay)))
-        if nmt:
-            jobs.append(('nmt', self.nmt_model, o.nmt_arena, (o.nmt_current_lr, (o.nmt_optim_alpha, o.nmt_optim_beta), o.nmt_optim_epsilon,
-                                                             o._nmt_steps, o.nmt_weight_decay)))
-        snaps = self.__dict__.setdefault('_snapshots', {})
-        with torch.no_grad():
-            for kind, model, arena, _ in jobs:
-                snap = snaps.get(kind)
-                if snap is None or snap.n != (arena.scalars_off if arena is not None else 0):
-                    snap = snaps[kind] = self._Snapshot(arena)
-                snap.take(model, arena)
-                on_gpu = on_gpu or any(p.is_cuda for p in model.parameters())
-        done = None
-        if on_gpu:
-            ready = torch.cuda.Event()
-            ready.record()
-            if getattr(self, '_copy_stream', None) is None:
-                self._copy_stream = torch.cuda.Stream()
-            with torch.cuda.stream(self._copy_stream), torch.no_grad():
-                self._copy_stream.wait_event(ready)
-                for kind, _, _, _ in jobs:
-                    snaps[kind].to_host()
-                done = torch.cuda.Event()
-                done.record()
-        else:
-            for kind, _, _, _ in jobs:
-                snaps[kind].to_host()
-        files = [(kind, arena, snaps[kind], adam) for kind, _, arena, adam in jobs]
-        self._save_error = None
-        self._save_thread = threading.Thread(target=self._write_checkpoint, args=(path, tag, done, files, state, kinds, rows))
-        self._save_thread.start()
-
-    def _write_checkpoint(self, path, tag, done, files, state, kinds, rows):
-        """The writer thread: waits for the copy stream's event, then writes every file from the pinned buffers."""
-        try:
-            if done is not None:
-                done.synchronize()
-            os.makedirs(path, exist_ok=True)
-            for kind, arena, snap, (lr, betas, eps, step, wd) in files:
-                self._write(snap.state_dict(), os.path.join(path, 'model_%s%s.pth' % (kind, tag)))
-                if arena is not None:
-                    self._write(arena.optimizer_state_from(snap.host[1:], lr, betas, eps, step, wd),
-                                os.path.join(path, 'optimizer_%s%s.pth' % (kind, tag)))
-            state['seed_counters'] = self._seed_counters_end(kinds, rows)
-            self._write(state, os.path.join(path, 'trainer_state' + tag + '.pth'))
-        except Exception as e:              # (handed to wait_for_save)
-            self._save_error = e
+        """save_models without the wait (Checkpointer.save_async); wait_for_save() joins the writer."""
+        self._checkpointer.save_async(tag)
 
     def wait_for_save(self):
         """Join the writer thread of the save in flight, if any, and re-raise what it failed with."""
-        t = getattr(self, '_save_thread', None)
-        if t is None:
-            return
-        t.join()
-        self._save_thread = None
-        err, self._save_error = self._save_error, None
-        if err is not None:
-            raise err
-
-    @staticmethod
-    def _read(path, names):
-        """The first of `names` that exists under `path`, loaded as data only (weights_only), else None."""
-        for name in names:
-            f = os.path.join(path, name)
-            if os.path.isfile(f):
-                return torch.load(f, map_location='cpu', weights_only=True)
-        return None
+        self._checkpointer.wait()
 
     def load_models(self, path=None, tag='-best'):
-        """Continue from what save_models(tag) wrote under `path` (default: opt.start_from, P/opts.py:37): the weights with the
-        BatchNorm buffers, the Adam state -- under the name save_models writes, optimizer_i2t{tag}.pth, or the one the reference
-        loads, i2t_optimizer.pth (P/misc/optimizer.py:80-87) -- and trainer_state.  The pivot NMT half is loaded when build_nmt
-        has run.  A missing optimizer or trainer_state file means weights only and a fresh optimizer, as in the reference, with a
-        warning; an unknown trainer_state version raises.  A file written at another world size loads: rank r takes the r-th seed
-        counter when there is one, else the first with its rank mixed in (_mix_rank_into_seed).  The carried next-batch
-        denominator, a prefetched batch and the gather events are not part of a checkpoint: they are reset."""
-        import warnings
-        self.wait_for_save()                     # (a save in flight reads the snapshot, not the arenas, but may be writing these files)
-        path = getattr(self.opt, 'start_from', None) if path is None else path
-        if path is None:
-            raise ValueError("load_models: no path given and opt.start_from is not set")
-        state = self._read(path, ['trainer_state' + tag + '.pth'])
-        if state is not None and state.get('format_version') != self.STATE_VERSION:
-            raise ValueError("trainer_state%s.pth has format version %r, this library reads version %d"
-                             % (tag, state.get('format_version'), self.STATE_VERSION))
-        if state is None:
-            warnings.warn("load_models: no trainer_state%s.pth under %s -- counters and seeds start afresh" % (tag, path))
-        if state is not None:
-            # before anything is written: a checkpoint of another --i2t_optim / --nmt_optim does not continue under this one
-            # (for the models whose files are there; a state without the key was written when every arena ran Adam)
-            for kind, method in (('i2t', self.method if self.i2t_model is not None else None),
-                                 ('nmt', self.optim.nmt_method if getattr(self, 'nmt_model', None) is not None else None)):
-                theirs = state.get(kind + '_optim', 'adam')
-                if method is not None and theirs != method and os.path.isfile(os.path.join(path, 'model_%s%s.pth' % (kind, tag))):
-                    raise ValueError("trainer_state%s.pth was written with %s_optim='%s', this run is configured with '%s'"
-                                     % (tag, kind, theirs, method))
-        seeds = state['seed_counters'] if state is not None else {}
-        rank = self.exchange.rank
-
-        def seed_for(kind, model):
-            c = seeds.get(kind)
-            if c:
-                model._seed_counter = int(c[rank]) if rank < len(c) else (int(c[0]) + 0x9E3779B1 * rank) & 0x7FFFFFFF
-
-        loaded = False
-        sd = self._read(path, ['model_i2t' + tag + '.pth']) if self.i2t_model is not None else None
-        if sd is not None:
-            loaded = True
-            if self.arena is None:
-                self.build_optimizer()
-            a = self.arena
-            if getattr(self, 'sharded', False):
-                dev = a.flat.device              # (all-gathers of an earlier step may still be writing the operand copy)
-                torch.cuda.current_stream(dev).wait_stream(self._comm(dev))
-            self.i2t_model.load_state_dict(sd)   # (in place: every parameter is its view of the arena)
-            osd = self._read(path, ['optimizer_i2t' + tag + '.pth', 'i2t_optimizer.pth'])
-            if osd is not None:
-                self._step, self.i2t_current_lr = a.import_optimizer_state(osd)
-            else:
-                warnings.warn("load_models: no optimizer_i2t%s.pth / i2t_optimizer.pth under %s -- weights only, fresh %s"
-                              % (tag, path, 'Adam' if a.method == 'adam' else a.method))
-                for buf in a.states:
-                    buf.zero_()
-                a.sync_operand_copy()
-                a.masters_stale = False
-                self._step, self.i2t_current_lr = 0, self.lr
-            if state is not None:
-                self.i2t_model.ss_prob = state['ss_prob']
-                self.sc_flag = state['sc_flag']
-                if osd is not None:
-                    self._step, self.i2t_current_lr = state['step'], state['i2t_current_lr']
-                seed_for('i2t', self.i2t_model)
-            gw = getattr(getattr(self.i2t_model, 'engine', None), 'gathered', None)
-            if gw is not None:
-                gw.events = [None] * 4           # (the operand copy was rebuilt on this stream: nothing to wait for)
-            self._next_den = None
-            self._prefetched = None
-            self._guard_pair = None
-        sd = self._read(path, ['model_nmt' + tag + '.pth']) if getattr(self, 'nmt_model', None) is not None else None
-        if sd is not None:
-            loaded = True
-            self.nmt_model.load_state_dict(sd)
-            osd = self._read(path, ['optimizer_nmt' + tag + '.pth', 'nmt_optimizer.pth'])
-            if osd is not None and not isinstance(osd, dict):
-                raise ValueError("the NMT optimizer file under %s is not a state dict" % path)
-            counters = dict(state['optim']) if (state is not None and state.get('optim') and osd is not None) else {}
-            if osd is None:
-                n = self.optim.nmt_arena
-                warnings.warn("load_models: no optimizer_nmt%s.pth / nmt_optimizer.pth under %s -- weights only, fresh %s"
-                              % (tag, path, 'Adam' if n.method == 'adam' else n.method))
-                for buf in n.states:
-                    buf.zero_()
-                self.optim._step = self.optim._nmt_steps = 0
-                self.optim.nmt_current_lr = self.optim.nmt_lr
-            else:
-                self.optim.load_state_dict(dict(counters, nmt=osd))
-            if state is not None:
-                seed_for('nmt', self.nmt_model)
-        if not loaded:
-            raise FileNotFoundError("load_models: neither model_i2t%s.pth nor model_nmt%s.pth for the models built here under %s"
-                                    % (tag, tag, path))
+        """Continue from what save_models(tag) wrote under `path` (default: opt.start_from): Checkpointer.load."""
+        self._checkpointer.load(path, tag)
